@@ -2,7 +2,7 @@
 """SAE train-step throughput on MI355X: activations/sec through the TopK-SAE train step
 (d = 384 -> 3072, k = 32), BASELINE.json's metric on its config 2 (1 GPU) / 3 (N GPUs).
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \\
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -10,6 +10,12 @@ A step = one full ``SAETrainer.train_step`` on a batch of B activation rows alre
 on-device ring buffer: stage + encode GEMM + TopK + sparse decode/MSE + weight-gradient GEMMs +
 (RCCL all-reduce for N > 1) + clip + AdamW + decoder renorm + dead-feature scan.  Weak scaling:
 B per GPU fixed, global batch = N * B.  Rank 0 prints ONE JSON line.
+
+A plain run times exactly K steps (one window) after the warm-up and prints the headline line.  ``--full`` adds
+what takes runs or time of its own: 9 windows of K steps (median reported), the probe window that picks the
+roofline kernel, the ``roofline`` / ``roofline_wgrad2`` / ``probe_kernel_us`` / ``strip_predict`` objects and the
+CPU baseline.  ``--dump-outputs DIR`` writes what the last timed step left to its caller (the module's parameters
+and buffers, the step's metrics) as ``DIR/<name>.npy``; the inputs depend on the arguments only.
 """
 
 from __future__ import annotations
@@ -18,7 +24,9 @@ import argparse
 import json
 import os
 import sys
+import tempfile
 import time
+import zlib
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent
@@ -30,6 +38,55 @@ D_MODEL, HIDDEN, TOPK = 384, 3072, 32
 BF16_DENSE_PEAK_TFLOPS = 2500.0  # MI355X dense bf16 MFMA peak (MI355X_MICROARCH.md, chip-level parameters)
 HBM_PEAK_GBS = 8000.0
 PMC_TRAFFIC_FILE = "r03_pmc_traffic.json"  # written by profiles/tools/profile_step.sh on this build
+DUMP_LIMIT_BYTES = 64 * 10**6  # --dump-outputs: all files together, npy headers included
+METRIC_FIELDS = ("loss", "reconstruction_loss", "sparsity_loss", "l0", "dead_feature_ratio", "grad_norm", "clip_coef",
+                 "learning_rate", "step")
+
+
+def step_outputs(model, metrics) -> dict:
+    """What a caller of ``SAETrainer.train_step`` holds after the step: the module's parameters and buffers (as
+    ``state_dict()`` hands them out; float32, integer buffers as float64) and the step's metrics (float64 scalars)."""
+    import numpy as np
+
+    out = {}
+    for name, t in model.state_dict().items():
+        t = t.detach().cpu()
+        out[name] = t.float().numpy() if t.is_floating_point() else t.double().numpy()
+    for f in METRIC_FIELDS:
+        v = getattr(metrics, f, None)
+        if v is not None:
+            out[f"metrics.{f}"] = np.array(float(v), dtype=np.float64)
+    return out
+
+
+def write_outputs(directory, arrays: dict, limit: int = DUMP_LIMIT_BYTES) -> dict:
+    """``directory/<name>.npy`` for every array (float32 / float64 kept, anything else as float64).  When the arrays
+    exceed ``limit`` bytes in all, each one larger than an even share of what is left is replaced by a fixed sample of
+    its flattened elements: sorted positions drawn without replacement by a generator seeded with the CRC-32 of the
+    name, so the sample depends on the name and size only.  Returns {name: (shape written, full shape)}."""
+    import numpy as np
+
+    arrays = {k: (a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)) for k, a in
+              ((k, np.asarray(v)) for k, v in arrays.items())}
+    header = 256  # upper bound of one .npy header
+    budget = limit - header * len(arrays)
+    if sum(a.nbytes for a in arrays.values()) + header * len(arrays) <= limit:
+        budget = None
+    Path(directory).mkdir(parents=True, exist_ok=True)
+    written = {}
+    left = len(arrays)
+    for name, a in sorted(arrays.items(), key=lambda kv: (kv[1].nbytes, kv[0])):
+        full_shape = a.shape
+        if budget is not None:
+            share = budget // left
+            if a.nbytes > share:
+                pos = np.random.default_rng(zlib.crc32(name.encode())).choice(a.size, share // a.itemsize, replace=False)
+                a = a.reshape(-1)[np.sort(pos)]
+            budget -= a.nbytes
+            left -= 1
+        np.save(Path(directory) / f"{name}.npy", a)
+        written[name] = (a.shape, full_shape)
+    return written
 
 
 def _cpu_leg(batch: int, budget_s: float, max_steps: int, cores: int) -> tuple:
@@ -133,9 +190,16 @@ def main() -> None:
     ap.add_argument("--batch", type=int, default=16384, help="activation rows per GPU per step")
     ap.add_argument("--ring-rows", type=int, default=1 << 22)
     ap.add_argument("--precision", choices=("bf16", "fp32"), default="bf16")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--windows", type=int, default=9,
-                    help="timed windows of --steps steps each; the median is reported (every window is listed: the first ~100 steps after an idle GPU run at a ramping clock)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: 9 windows (unless --windows), the probe window and the "
+                         "roofline objects, strip_predict, the CPU baseline (unless --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (parameters and buffers of the module, the step's "
+                         "metrics) as DIR/<name>.npy, float32 / float64, at most 64 MB in all (seeded samples beyond)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--windows", type=int, default=None,
+                    help="timed windows of --steps steps each; the median is reported (every window is listed: the first "
+                         "~100 steps after an idle GPU run at a ramping clock).  Default 1, 9 with --full")
     ap.add_argument("--grad-exchange", choices=("auto", "fp32", "bf16"), default="auto",
                     help="N > 1: dtype of the gradient all-reduce; auto (the bench default) = bf16 in the bf16 mode, fp32 in the "
                          "fp32 mode - named in the line's config.workload / config.grad_exchange; the library default "
@@ -147,6 +211,10 @@ def main() -> None:
     ap.add_argument("--relu", action="store_true", help="informational: ReLU+L1 SAE step (row A12) instead of the TopK "
                                                         "headline; no roofline object")
     args = ap.parse_args()
+    full = args.full
+    n_windows = args.windows if args.windows is not None else (9 if full else 1)
+    if n_windows < 1 or args.steps < 1 or args.warmup < 0:
+        ap.error("--steps and --windows must be at least 1, --warmup at least 0")
 
     global D_MODEL, HIDDEN, TOPK
     if args.dims:
@@ -187,12 +255,15 @@ def main() -> None:
     cfg = TrainingConfig(batch_size=B, learning_rate=1e-4, weight_decay=0.0, warmup_steps=1000, gradient_clip=1.0,
                          use_amp=(args.precision == "bf16"), num_workers=0, seed=42,
                          grad_exchange_dtype=args.grad_exchange)
-    trainer = SAETrainer(model, cfg, device=device, run_dir=ROOT / "gpurun_out" / f"bench_rank{rank}")
+    # the trainer keeps a run directory for checkpoints; the bench writes none, and the checkout it runs from may be
+    # read-only, so the directory is a temporary one, removed at exit
+    run_dir = tempfile.TemporaryDirectory(prefix=f"wsae_bench_rank{rank}_")
+    trainer = SAETrainer(model, cfg, device=device, run_dir=run_dir.name)
     ring_dtype = torch.bfloat16 if args.precision == "bf16" else torch.float32
     ring = ActivationRing(args.ring_rows, D_MODEL, device=device, dtype=ring_dtype)
     ring.fill_synthetic(args.ring_rows, seed=42 + rank)  # every rank owns its own shard of rows
     loader = RingLoader(ring, B, shuffle=True, seed=42)
-    total = args.warmup + (args.windows + 1) * args.steps + 8 + 224
+    total = args.warmup + (n_windows + 1) * args.steps + 8 + 224
     trainer.setup_scheduler(max(total, 20000))
 
     def batches():
@@ -213,36 +284,39 @@ def main() -> None:
     eng = model._engine
     prec = N.PREC_BF16 if args.precision == "bf16" else N.PREC_FP32
     handle = eng.ctx(prec, B)
-    # Which kernel is the dominant one is MEASURED, not assumed: an untimed probe window with HIP events around every
-    # launch (recorded by the library on the launch stream) ranks the step's kernels by average duration; the timed
-    # windows then carry events around that kernel only (two event records per step).
+    # Which kernel is the dominant one is MEASURED, not assumed (--full): an untimed probe window with HIP events around
+    # every launch (recorded by the library on the launch stream) ranks the step's kernels by average duration; the timed
+    # windows then carry events around that kernel only (two event records per step).  A plain run records no events.
     probe = {}
     n_settle = n_probe = 0
     if not args.profile_all:
-        # (the ranking is only meaningful at the clock the timed windows run at: an idle GPU needs ~100 steps to get there, so
-        # with a short --warmup the probe is preceded by enough plain steps to make 200 untimed steps in all; the line reports
-        # every untimed step)
-        n_probe = 24
+        # (the timed windows - and the ranking - are only meaningful at the clock of a busy GPU: an idle one needs ~100 steps
+        # to get there, so with a short --warmup enough plain steps follow it to make 200 untimed steps in all; the line
+        # reports every untimed step)
+        n_probe = 24 if full else 0
         n_settle = max(0, 200 - args.warmup - n_probe)
         for _ in range(n_settle):
             trainer.train_step(next(it))
-        N.check(N.lib().wsae_profile_enable(handle, -1, n_probe), "wsae_profile_enable")
-        for _ in range(n_probe):
-            trainer.train_step(next(it))
-        probe = N.profile_read(handle)
-        N.check(N.lib().wsae_profile_disable(handle), "wsae_profile_disable")
+        if n_probe:
+            N.check(N.lib().wsae_profile_enable(handle, -1, n_probe), "wsae_profile_enable")
+            for _ in range(n_probe):
+                trainer.train_step(next(it))
+            probe = N.profile_read(handle)
+            N.check(N.lib().wsae_profile_disable(handle), "wsae_profile_disable")
     kid = -1
     dominant = None
     if probe:
         dominant = max(probe, key=lambda k: probe[k][1] / max(probe[k][0], 1))
         kid = next(k for k in range(N.KERNEL_COUNT) if N.lib().wsae_kernel_name(k).decode() == dominant)
-    N.check(N.lib().wsae_profile_enable(handle, kid, args.steps * args.windows), "wsae_profile_enable")
+    events = full or args.profile_all
+    if events:
+        N.check(N.lib().wsae_profile_enable(handle, kid, args.steps * n_windows), "wsae_profile_enable")
 
     # windows of EXACTLY --steps steps, each bracketed by barrier + synchronize on both
     # sides and reduced with MAX over ranks; the median window is the reported one, all of them are listed.
     last = None
     windows = []
-    for _ in range(max(args.windows, 1)):
+    for _ in range(n_windows):
         barrier()
         t0 = time.perf_counter()
         for _ in range(args.steps):
@@ -256,8 +330,10 @@ def main() -> None:
         windows.append(el)
     elapsed = sorted(windows)[len(windows) // 2]
 
-    prof = N.profile_read(handle)
-    N.check(N.lib().wsae_profile_disable(handle), "wsae_profile_disable")
+    prof = {}
+    if events:
+        prof = N.profile_read(handle)
+        N.check(N.lib().wsae_profile_disable(handle), "wsae_profile_disable")
 
     if rank == 0:
         value = world * B * args.steps / elapsed
@@ -269,7 +345,7 @@ def main() -> None:
         headline = not args.dims and not args.relu
         pmc_k = {}
         pmc = ROOT / "profiles" / PMC_TRAFFIC_FILE
-        if headline and B == 16384 and args.precision == "bf16" and pmc.exists():
+        if full and headline and B == 16384 and args.precision == "bf16" and pmc.exists():
             pmc_k = json.loads(pmc.read_text())["kernels"]
 
         pmc_names = {"encode_gemm": "encode_gemm256d_kernel", "topk": "topk_strips_kernel", "decode": "decode_mfma_kernel",
@@ -285,7 +361,7 @@ def main() -> None:
                                           f"{pmc_names[name]})")
             return None
 
-        if headline:
+        if full and headline:
             names = dict(prof)
             halves = 2 if (world > 1 and cfg.ddp_overlap_halves and N.lib().wsae_wgrad_parts_supported(handle)) else 1
 
@@ -326,16 +402,15 @@ def main() -> None:
                        "lr": 1e-4, "clip": 1.0, "parallelism": f"dp{world}",
                        **({"grad_exchange": trainer.grad_exchange} if world > 1 else {})},
             **({"rehearsal": True} if rehearse else {}),
-            "roofline": roof,
-            "roofline_wgrad2": roof_wgrad,
-            "probe_kernel_us": {k: round(v[1] / max(v[0], 1) * 1e3, 2) for k, v in probe.items()},
+            **({"roofline": roof, "roofline_wgrad2": roof_wgrad,
+                "probe_kernel_us": {k: round(v[1] / max(v[0], 1) * 1e3, 2) for k, v in probe.items()}} if full else {}),
             "untimed_steps_before_windows": {"warmup": args.warmup, "settle": n_settle, "probe": n_probe},
             "step_dense_equiv_frac": value * f_dense / 1e12 / BF16_DENSE_PEAK_TFLOPS,
             "final_loss": last.loss if last is not None else None,
         }
         if args.profile_all:
             out["kernel_ms_per_step"] = {k: v[1] / max(v[0], 1) for k, v in prof.items()}
-        if not args.relu:
+        if full and not args.relu:
             # selective strip stores of the encoder GEMM (include/wsae.h): rows that had to recompute strips over the whole
             # run (warm-up, timed windows, probe) and the last batch's smallest row threshold
             import ctypes
@@ -344,7 +419,9 @@ def main() -> None:
                     "wsae_ctx_strip_stats")
             out["strip_predict"] = {"enabled": os.environ.get("WSAE_STRIP_PREDICT", "1") != "0", "refilled_rows": rows_c.value,
                                     "last_min_threshold": tmin_c.value, "margin": s_c.value}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.dump_outputs:
+            write_outputs(args.dump_outputs, step_outputs(model, last))
+        if full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(B)
         print(json.dumps(out))
     if world > 1:

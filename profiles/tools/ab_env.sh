@@ -10,7 +10,7 @@ kv, rounds, extra = sys.argv[1], int(sys.argv[2]), sys.argv[3:]
 k, v = kv.split("=", 1)
 for r in range(rounds):
     for tag, env in (("A", dict(os.environ)), ("B", dict(os.environ, **{k: v}))):
-        base = [sys.executable, "bench.py", "--no-cpu-baseline", "--steps", "100", "--warmup", "100"] + extra
+        base = [sys.executable, "bench.py", "--full", "--no-cpu-baseline", "--steps", "100", "--warmup", "100"] + extra
         o = subprocess.run(base + ["--profile-all"], env=env, capture_output=True, text=True)
         line = [l for l in o.stdout.splitlines() if l.startswith("{")]
         if not line:

@@ -25,6 +25,7 @@ Golden sets (SURVEY.md row C list):
   G16 CrossLayerCrosscoder (ReLU + decoder-norm-weighted L1): forward, every gradient, clock
   G17 extraction driver: extract_and_cache_features on the seeded tiny Whisper -> cache tensors + metadata (N2)
   G4b 20-step trajectory at cfg2 dimensions (384 -> 3072, k = 32): loss / lr / l0 scalars + sampled final parameters
+  G18 FeatureCache interchange, the other way: a cache written by THIS build, as the reference's FeatureCache.load reads it
 
 ``python tests/golden/make_golden.py g10 g11`` regenerates only the named sets.
 """
@@ -32,6 +33,8 @@ Golden sets (SURVEY.md row C list):
 from __future__ import annotations
 
 import json
+import os
+import subprocess
 import sys
 import tempfile
 from pathlib import Path
@@ -612,8 +615,38 @@ def g17_extraction_driver():
     np.savez_compressed(HERE / "g17_extraction.npz", **out)
 
 
+def g18_cache_read_by_reference():
+    """A cache written by THIS build's FeatureCache.save (a child process on the repository's own package), then read by
+    the reference's FeatureCache.load: the sidecar the reference accepted and what its load returned."""
+    from whisper_sae.config import DataConfig, WhisperConfig  # reference
+    from whisper_sae.data.feature_cache import FeatureCache  # reference
+    repo = HERE.parents[1]
+    code = ("import sys, torch\n"
+            "from pathlib import Path\n"
+            "from oracle import synth\n"
+            "from whisper_sae.config import DataConfig, WhisperConfig\n"
+            "from whisper_sae.data import FeatureCache\n"
+            "feats = torch.from_numpy(synth.activations(40, 384, seed=9, stream=0, bf16=False))\n"
+            "fc = FeatureCache(Path(sys.argv[1]), WhisperConfig(), DataConfig(cache_dir=Path('cache')))\n"
+            "fc.save(feats, 'decoder', 3, num_samples=5)\n")
+    env = dict(os.environ, PYTHONPATH=os.pathsep.join((str(repo), str(repo / "whisper-sae_amd"))), PYTHONDONTWRITEBYTECODE="1")
+    with tempfile.TemporaryDirectory() as td:
+        subprocess.run([sys.executable, "-c", code, td], env=env, check=True)
+        fc = FeatureCache(Path(td), WhisperConfig(), DataConfig())
+        assert fc.has_cache("decoder", 3)
+        feats, meta = fc.load("decoder", 3)
+        sidecar = json.loads(fc._get_metadata_path("decoder", 3).read_text())
+    sidecar["created_at"] = "2026-01-01T00:00:00"  # pinned so that regenerating the fixture is byte-stable
+    read = {"type": type(feats).__name__, "shape": list(feats.shape), "dtype": str(feats.dtype),
+            "sum": float(feats.double().sum()), "model_name": meta.model_name, "component": meta.component,
+            "layer_idx": meta.layer_idx, "hidden_dim": meta.hidden_dim, "num_samples": meta.num_samples,
+            "num_tokens": meta.num_tokens}
+    (HERE / "g18_cache_read_by_reference.json").write_text(json.dumps({"sidecar": sidecar, "reference_read": read},
+                                                                      indent=1) + "\n")
+
+
 SETS = {"g17": g17_extraction_driver, "g16": g16_crosscoder_relu, "g15": g15_crosscoder, "g14": g14_hooks, "g13": g13_feature_topk, "g12": g12_transcoders, "g1": g1_g2_g3, "g4": g4_trajectory, "g4b": g4b_trajectory_cfg2, "g5": g5_lr, "g6": g6_dead, "g7": g7_resample, "g8": g8_relu,
-        "g10": g10_seeded_init, "g11": g11_cache_interchange}
+        "g10": g10_seeded_init, "g11": g11_cache_interchange, "g18": g18_cache_read_by_reference}
 
 if __name__ == "__main__":
     for name in (sys.argv[1:] or list(SETS)):

@@ -1,13 +1,11 @@
 """CPU pins that round 1 claimed but did not commit: the torch-CPU restatement that ``bench.py`` times
 as ``cpu_baseline`` against the reference's own train steps (G3 / G4), the drop-in modules' seeded initialisation
-against the reference's (G10), and the activation-cache interchange with the reference's ``FeatureCache`` (G11, N1)."""
+against the reference's (G10), and the activation-cache interchange with the reference's ``FeatureCache``, both ways
+(G11, G18, N1)."""
 
 from __future__ import annotations
 
 import json
-import os
-import subprocess
-import sys
 from pathlib import Path
 
 import numpy as np
@@ -16,8 +14,6 @@ import torch
 
 from oracle import synth
 from oracle.torch_step import TorchCPUStep
-
-REFERENCE_SRC = Path("/root/reference/src")
 
 
 def rel(a, b):
@@ -128,27 +124,29 @@ class TestCacheInterchange:
         assert mine["data_config"].keys() == ref["data_config"].keys()
         assert fc._get_cache_path("encoder", 0).name == "whisper-tiny_encoder_layer0.pt"
 
-    @pytest.mark.skipif(not REFERENCE_SRC.exists(), reason="the reference only exists in the build container")
-    def test_the_reference_reads_a_cache_this_build_wrote(self, tmp_path):
+    def test_the_reference_reads_a_cache_this_build_wrote(self, golden_dir, tmp_path):
+        """G18 (tests/golden/make_golden.py): the reference's ``FeatureCache.load`` read a cache this build wrote - a bare
+        tensor for ``torch.load(weights_only=True)`` and a sidecar whose fields become the reference's metadata record
+        one for one.  What this build writes now must be that cache: the same fields in the same order with the same
+        JSON types and values, and a tensor that loads to what the reference got."""
         from whisper_sae.config import DataConfig, WhisperConfig
         from whisper_sae.data import FeatureCache
+        g = json.loads((golden_dir / "g18_cache_read_by_reference.json").read_text())
         feats = torch.from_numpy(synth.activations(40, 384, seed=9, stream=0, bf16=False))
-        FeatureCache(tmp_path, WhisperConfig(), DataConfig(cache_dir=Path("cache"))).save(feats, "decoder", 3, num_samples=5)
-        code = (
-            "import sys, json, torch\n"
-            "from pathlib import Path\n"
-            "from whisper_sae.config import DataConfig, WhisperConfig\n"
-            "from whisper_sae.data.feature_cache import FeatureCache\n"
-            "fc = FeatureCache(Path(sys.argv[1]), WhisperConfig(), DataConfig())\n"
-            "assert fc.has_cache('decoder', 3)\n"
-            "f, m = fc.load('decoder', 3)\n"
-            "print(json.dumps({'shape': list(f.shape), 'sum': float(f.double().sum()), 'tokens': m.num_tokens,\n"
-            "                  'samples': m.num_samples, 'dim': m.hidden_dim, 'component': m.component}))\n")
-        env = dict(os.environ, PYTHONPATH=str(REFERENCE_SRC), PYTHONDONTWRITEBYTECODE="1")
-        out = subprocess.run([sys.executable, "-c", code, str(tmp_path)], env=env, capture_output=True, text=True,
-                             timeout=300)
-        assert out.returncode == 0, out.stderr[-2000:]
-        got = json.loads(out.stdout.strip().splitlines()[-1])
-        assert got["shape"] == [40, 384] and got["tokens"] == 40 and got["samples"] == 5 and got["dim"] == 384
-        assert got["component"] == "decoder"
-        assert got["sum"] == float(feats.double().sum())
+        fc = FeatureCache(tmp_path, WhisperConfig(), DataConfig(cache_dir=Path("cache")))
+        fc.save(feats, "decoder", 3, num_samples=5)
+        sidecar = json.loads(fc._get_metadata_path("decoder", 3).read_text())
+        want = g["sidecar"]
+        assert list(sidecar) == list(want) and list(sidecar["data_config"]) == list(want["data_config"])
+        assert {k: type(v).__name__ for k, v in sidecar.items()} == {k: type(v).__name__ for k, v in want.items()}
+        assert {k: type(v).__name__ for k, v in sidecar["data_config"].items()} == \
+            {k: type(v).__name__ for k, v in want["data_config"].items()}
+        assert {k: v for k, v in sidecar.items() if k != "created_at"} == {k: v for k, v in want.items() if k != "created_at"}
+        f = torch.load(fc._get_cache_path("decoder", 3), weights_only=True)
+        ref = g["reference_read"]
+        assert type(f).__name__ == ref["type"] and list(f.shape) == ref["shape"] == [40, 384] and str(f.dtype) == ref["dtype"]
+        assert float(f.double().sum()) == ref["sum"] == float(feats.double().sum())
+        assert (sidecar["num_tokens"], sidecar["num_samples"], sidecar["hidden_dim"]) == \
+            (ref["num_tokens"], ref["num_samples"], ref["hidden_dim"]) == (40, 5, 384)
+        assert (sidecar["component"], sidecar["layer_idx"], sidecar["model_name"]) == \
+            (ref["component"], ref["layer_idx"], ref["model_name"]) == ("decoder", 3, "openai/whisper-tiny")

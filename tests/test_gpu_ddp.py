@@ -170,7 +170,7 @@ def test_bench_rehearses_two_ranks_on_one_gpu(tmp_path):
     env = dict(os.environ, WSAE_BENCH_REHEARSE="1", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), str(root / "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
-           "--windows", "2", "--batch", "2048", "--ring-rows", "65536", "--no-cpu-baseline"]
+           "--windows", "2", "--batch", "2048", "--ring-rows", "65536", "--no-cpu-baseline", "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=tmp_path)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
