@@ -40,7 +40,7 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from .synth import bf16_round
+from .synth import bf16_round, topk_margin
 
 F32 = np.float32
 F64 = np.float64
@@ -146,6 +146,19 @@ def check_selection(pre: np.ndarray, idx: np.ndarray, k: int, rtol: float = 1e-5
     must = pre64 > (kth + slack)[:, None]
     may = pre64 >= (kth - slack)[:, None]
     return distinct & ~(must & ~sel).any(axis=1) & ~(sel & ~may).any(axis=1)
+
+
+def reconcile_selection(st: SAEState, x: np.ndarray, idx_dev: np.ndarray, k: int, mode: str):
+    """Device index sets vs the oracle's: exact on clear-margin rows, valid-up-to-noise elsewhere.
+    Returns (selection for the oracle to continue from, fraction of clear rows)."""
+    pre = pre_activation(st, x, mode)
+    _, idx_o = topk_select(pre, k)
+    clear = topk_margin(pre, k) > 1e-5
+    dev_sets, ora_sets = np.sort(idx_dev, axis=1), np.sort(idx_o, axis=1)
+    assert np.array_equal(dev_sets[clear], ora_sets[clear]), "TopK index sets differ on clear-margin rows"
+    assert check_selection(pre, idx_dev, k, rtol=1e-5).all(), "a device selection is not a TopK of its row"
+    sel = np.where(clear[:, None], idx_o, idx_dev.astype(np.int64))
+    return sel, float(clear.mean())
 
 
 def densify(vals: np.ndarray, idx: np.ndarray, hidden_dim: int) -> np.ndarray:

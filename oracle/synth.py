@@ -37,6 +37,14 @@ def counter_u64(n: int, seed: int, stream: int = 0) -> np.ndarray:
     return _splitmix64(ctr & _MASK64)
 
 
+def index_set_digest(idx: np.ndarray) -> np.ndarray:
+    """Per-row 32-bit digest of a set of indices ([B, k] -> uint32 [B]): the wrapping sum of the splitmix64 hashes of the
+    members, independent of their order.  Goldens store it in place of every row's index set."""
+    h = _splitmix64(np.asarray(idx, dtype=np.int64).astype(np.uint64))
+    with np.errstate(over="ignore"):
+        return (h.sum(axis=1, dtype=np.uint64) & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+
+
 def bf16_round(a: np.ndarray) -> np.ndarray:
     """Round float32 to the nearest bfloat16 (ties to even); result returned as float32.
 

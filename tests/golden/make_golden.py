@@ -26,6 +26,7 @@ Golden sets (SURVEY.md row C list):
   G17 extraction driver: extract_and_cache_features on the seeded tiny Whisper -> cache tensors + metadata (N2)
   G4b 20-step trajectory at cfg2 dimensions (384 -> 3072, k = 32): loss / lr / l0 scalars + sampled final parameters
   G18 FeatureCache interchange, the other way: a cache written by THIS build, as the reference's FeatureCache.load reads it
+  G19 forward + gradients at the benchmarked batch (cfg2 dimensions, B = 16384 clear-margin rows of a longer stream)
 
 ``python tests/golden/make_golden.py g10 g11`` regenerates only the named sets.
 """
@@ -645,7 +646,54 @@ def g18_cache_read_by_reference():
                                                                       indent=1) + "\n")
 
 
-SETS = {"g17": g17_extraction_driver, "g16": g16_crosscoder_relu, "g15": g15_crosscoder, "g14": g14_hooks, "g13": g13_feature_topk, "g12": g12_transcoders, "g1": g1_g2_g3, "g4": g4_trajectory, "g4b": g4b_trajectory_cfg2, "g5": g5_lr, "g6": g6_dead, "g7": g7_resample, "g8": g8_relu,
+def g19_bench_batch():
+    """G19: the reference's forward and autograd at the benchmarked batch (cfg-2 dimensions, B = 16384), where the build
+    runs the persistent encoder GEMM, the strip-guided TopK, the chunked decode and the split-K weight gradients.  The
+    batch is the first 16384 rows of a synthetic stream whose k / k+1 margin under the reference is above 1e-4 relative:
+    only their indices are stored, the test regenerates x from ``synth``.  To keep the file small, every row's index set
+    is stored as its ``synth.index_set_digest`` (the sets themselves for the 128 sampled rows), every row's squared
+    reconstruction error as one number, and the reconstruction itself for the sampled rows."""
+    D, H, K, B, N = 384, 3072, 32, 16384, 20480
+    w = synth.sae_weights(D, H, seed=42, bf16=True, b_pre_scale=0.1)
+    stream = synth.activations(N, D, seed=42, stream=19, bf16=True)
+    torch.manual_seed(0)
+    m = TopKSAE(D, H, k=K, dead_feature_threshold=1000)
+    load_weights(m, w)
+    m.train()
+    with torch.no_grad():
+        pre_all = m.encoder(torch.from_numpy(stream) - m.b_pre).numpy()
+    margin = synth.topk_margin(pre_all, K)
+    rows = np.flatnonzero(margin > 1e-4)[:B].astype(np.int32)
+    assert rows.size == B, f"only {rows.size} rows of {N} have a clear k / k+1 margin"
+    x = stream[rows]
+    out = m(torch.from_numpy(x))
+    _, idx = torch.topk(torch.from_numpy(pre_all[rows]), K, dim=-1)
+    out.loss.backward()
+    grads = {"W_e": m.encoder.weight.grad, "b_e": m.encoder.bias.grad, "W_d": m.decoder.weight.grad,
+             "b_d": m.decoder.bias.grad, "b_pre": m.b_pre.grad}
+    grads = {k_: v.detach().numpy().copy() for k_, v in grads.items()}
+    pos_r = np.unique((synth.counter_u64(128, 19, 97) % np.uint64(B)).astype(np.int32))
+    recon = out.reconstructed.detach().numpy()
+    resid = recon.astype(np.float64) - x.astype(np.float64)
+    sets = np.sort(idx.numpy(), axis=1)
+    pos_e = sample_positions((H, D), 4096, 19)
+    pos_d = sample_positions((D, H), 4096, 20)
+    np.savez_compressed(
+        HERE / "g19_bench_batch.npz",
+        dims=np.array([D, H, K, B]), stream_rows=np.array([N]), rows=rows,
+        idx_digest=synth.index_set_digest(sets), idx_rows=sets[pos_r].astype(np.int16),
+        min_margin=np.float64(margin[rows].min()),
+        loss=np.float32(out.loss.item()), l0=np.float32(out.l0.item()),
+        last_activated=m.feature_last_activated.numpy().copy(), step_count=np.int64(m.step_count.item()),
+        recon_rows=pos_r, recon=recon[pos_r], row_sse=(resid * resid).sum(axis=1).astype(np.float32),
+        norms=np.array([np.sqrt((grads[n].astype(np.float64) ** 2).sum()) for n in ("W_e", "b_e", "W_d", "b_d", "b_pre")]),
+        b_e=grads["b_e"], b_d=grads["b_d"], b_pre=grads["b_pre"],
+        pos_e=pos_e, W_e_samples=grads["W_e"].reshape(-1)[pos_e],
+        pos_d=pos_d, W_d_samples=grads["W_d"].reshape(-1)[pos_d],
+    )
+
+
+SETS = {"g19": g19_bench_batch, "g17": g17_extraction_driver, "g16": g16_crosscoder_relu, "g15": g15_crosscoder, "g14": g14_hooks, "g13": g13_feature_topk, "g12": g12_transcoders, "g1": g1_g2_g3, "g4": g4_trajectory, "g4b": g4b_trajectory_cfg2, "g5": g5_lr, "g6": g6_dead, "g7": g7_resample, "g8": g8_relu,
         "g10": g10_seeded_init, "g11": g11_cache_interchange, "g18": g18_cache_read_by_reference}
 
 if __name__ == "__main__":

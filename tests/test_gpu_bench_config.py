@@ -82,19 +82,6 @@ def ring_batch(device, D, B, seed, n_rows):
     return ring, batch, x
 
 
-def reconcile_selection(st, x, idx_dev, K, mode):
-    """Device index sets vs the oracle's: exact on clear-margin rows, valid-up-to-noise elsewhere.
-    Returns (selection for the oracle to continue from, fraction of clear rows)."""
-    pre = O.pre_activation(st, x, mode)
-    _, idx_o = O.topk_select(pre, K)
-    clear = synth.topk_margin(pre, K) > 1e-5
-    dev_sets, ora_sets = np.sort(idx_dev, axis=1), np.sort(idx_o, axis=1)
-    assert np.array_equal(dev_sets[clear], ora_sets[clear]), "TopK index sets differ on clear-margin rows"
-    assert O.check_selection(pre, idx_dev, K, rtol=1e-5).all(), "a device selection is not a TopK of its row"
-    sel = np.where(clear[:, None], idx_o, idx_dev.astype(np.int64))
-    return sel, float(clear.mean())
-
-
 def one_step_against_oracle(device, tmp_path, D, H, K, B, seed, tag, lr=1e-4, n_rows=None):
     from whisper_sae.config import TrainingConfig
     from whisper_sae.sae.training import SAETrainer
@@ -109,7 +96,7 @@ def one_step_against_oracle(device, tmp_path, D, H, K, B, seed, tag, lr=1e-4, n_
     work = eng.work(B)
     idx_dev = work["idx"].cpu().numpy()
     assert idx_dev.shape == (B, K)
-    sel, clear_frac = reconcile_selection(st, x, idx_dev, K, "amp")
+    sel, clear_frac = O.reconcile_selection(st, x, idx_dev, K, "amp")
     assert clear_frac > 0.98
     st0 = st.copy()
     r = O.train_step(st, x, lr, "amp", max_norm=1.0, select=sel)
@@ -179,7 +166,7 @@ class TestBenchConfiguration:
         out = m(xt)
         out.loss.backward()
         _, idx = m._last_code
-        sel, _ = reconcile_selection(st, x, idx.cpu().numpy(), K, "amp")
+        sel, _ = O.reconcile_selection(st, x, idx.cpu().numpy(), K, "amp")
         fwd = O.forward(st.copy(), x, "amp", select=sel)
         ora = O.backward(st, x, fwd, "amp")
         assert abs(float(out.loss.detach()) - float(fwd["loss"])) / float(fwd["loss"]) < 1e-5
