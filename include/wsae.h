@@ -189,6 +189,35 @@ int wsae_weight_grads(wsae_ctx* ctx, const float* params, const void* x, int32_t
                       const int32_t* rows, const float* vals, const int32_t* idx,
                       const float* dpre, int32_t B, float* grads, void* stream);
 
+/* ---- BatchTopK (Bussmann, Leask & Nanda 2024) ------------------------------------------------
+ * Over the compact code of the per-row TopK (vals [B, k] with k = the ctx's k, here the per-row cap k_max; each row sorted
+ * descending): t = the (B k_batch)-th largest POSITIVE value of the batch (the smallest positive one when there are fewer);
+ * a candidate is kept iff v > 0 and v >= t (ties at t all kept), every other one is overwritten with 0.0f (its index is
+ * left in place).  Decode, backward, l0 and the dead-feature clock treat v <= 0 as inactive, so the masked code feeds
+ * them unchanged.  Modes:
+ *   WSAE_BTK_TRAIN   select as above and update the threshold: theta <- t while theta < 0, else
+ *                    theta <- beta theta + (1 - beta) t (no update when nothing was kept);
+ *   WSAE_BTK_EVAL    keep iff v > 0 and v > theta; while theta < 0 (never trained) select as above, without update;
+ *   WSAE_BTK_SELECT  select as above without touching theta (training-mode encode, resampling forwards).
+ * The state record is caller-owned device memory; everything runs on the stream, with no host sync. */
+#define WSAE_BTK_TRAIN 0
+#define WSAE_BTK_EVAL 1
+#define WSAE_BTK_SELECT 2
+typedef struct wsae_batch_topk_state {
+    float threshold;        /* theta, -1 = never trained (set by the caller at creation) */
+    float beta;             /* EMA factor of theta (set by the caller) */
+    float last_t;           /* t of the last selection (theta in threshold mode), -1 when no candidate was positive */
+    int32_t saturated_rows; /* rows whose k_max-th candidate was kept (0 when k_max = hidden_dim) */
+    int32_t kept;           /* entries kept by the last selection */
+    int32_t reserved[3];
+} wsae_batch_topk_state;
+/* The selection alone, in place on vals [B, ctx k] (16-byte aligned); 1 <= k_batch <= ctx k. */
+int wsae_batch_topk_select(wsae_ctx* ctx, float* vals, int32_t B, int32_t k_batch, int32_t mode,
+                           wsae_batch_topk_state* state, void* stream);
+/* Run the selection inside wsae_encode_topk and wsae_encode_decode, between the TopK and the decode (k_batch = 0, the
+ * default: off - no extra launch, outputs bit-identical to a ctx that never heard of it).  `state` must outlive the calls. */
+int wsae_ctx_set_batch_topk(wsae_ctx* ctx, int32_t k_batch, int32_t mode, wsae_batch_topk_state* state);
+
 /* ---- data parallel: the gradients go straight onto the exchange buffer -------------------------------------------
  * (absent from the reference, which is single-process).  The WIRE is what the ranks
  * all-reduce(SUM): `hidden_dim * input_dim` elements of dW_dT, then dW_e, db_e, db_d, db_pre (the rest of the pack) and

@@ -126,6 +126,10 @@ struct wsae_ctx {
     int n_dec_blocks;     // blocks used by the last decode launch (partials to reduce)
     int n_sq_parts;       // global-norm partials left in part_sq by the last wsae_weight_grads
     float* dbd2;          // [64][D] level-1 reduction of part_dbd
+    int32_t* btk_ws;      // histograms and counters of the BatchTopK selection (wsae_batch_topk.hip)
+    int btk_k;            // wsae_ctx_set_batch_topk: k per row of the batch-wide selection (0 = off, the default)
+    int btk_mode;         // WSAE_BTK_*
+    wsae_batch_topk_state* btk_state;
     size_t ws_bytes;
 };
 
@@ -277,6 +281,10 @@ int wsae_internal_topk(wsae_ctx* ctx, int B, float* vals, int32_t* idx, int32_t*
 int wsae_internal_encode_topk(wsae_ctx* ctx, const float* params, const void* x, int x_dtype, const int32_t* rows, int B,
                               float* vals, int32_t* idx, int64_t* step_count, int32_t* fb, hipStream_t st);
 bool wsae_internal_strips_ok(const wsae_ctx* ctx);
+// internal (wsae_batch_topk.hip): the batch-wide selection over the compact code vals [B][K]; its workspace size
+size_t wsae_internal_batch_topk_ws_bytes();
+int wsae_internal_batch_topk(wsae_ctx* ctx, float* vals, int B, int k_batch, int mode, wsae_batch_topk_state* state,
+                             hipStream_t st);
 // internal (wsae_decode_mfma.hip): the MFMA decode kernel (BF16 mode)
 bool wsae_internal_decode_mfma_ok(const wsae_ctx* c);
 int wsae_internal_decode_mfma(wsae_ctx* c, const float* params, const void* x, int x_dtype, const int32_t* rows,

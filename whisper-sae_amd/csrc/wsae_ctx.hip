@@ -120,6 +120,7 @@ extern "C" int wsae_ctx_create(const wsae_config* cfg, wsae_ctx** out) {
     const size_t o_dl = cv.take((size_t)H * 4);
     const size_t o_ro = cv.take((size_t)maxB * 4);
     const size_t o_tm = cv.take(TG_WORDS * 4);
+    const size_t o_bt = cv.take(wsae_internal_batch_topk_ws_bytes());
     char* base = nullptr;
     hipError_t e = hipMalloc((void**)&base, cv.total);
     if (e != hipSuccess) {
@@ -161,6 +162,7 @@ extern "C" int wsae_ctx_create(const wsae_config* cfg, wsae_ctx** out) {
     c->dead_list = (int32_t*)(base + o_dl);
     c->row_order = (int32_t*)(base + o_ro);
     c->tmin = (uint32_t*)(base + o_tm);
+    c->btk_ws = (int32_t*)(base + o_bt);
     const char* sp = getenv("WSAE_STRIP_PREDICT");  // (A/B runs: "0" creates contexts with the selective strip stores off)
     c->strip_predict = (sp && sp[0] == '0') ? 0 : 1;
     const char* ss = getenv("WSAE_STRIP_SAFETY");

@@ -625,6 +625,10 @@ extern "C" int wsae_encode_decode(wsae_ctx* ctx, const float* params, const void
     hipStream_t st = (hipStream_t)stream;
     rc = wsae_internal_encode_topk(ctx, params, x, x_dtype, rows, B, vals, idx, step_count, &stats->topk_fallback_rows, st);
     if (rc) return rc;
+    if (ctx->btk_k) {  // BatchTopK (wsae_ctx_set_batch_topk): the batch-wide selection zeroes the dropped candidates
+        rc = wsae_internal_batch_topk(ctx, vals, B, ctx->btk_k, ctx->btk_mode, ctx->btk_state, st);
+        if (rc) return rc;
+    }
     return decode_launch(ctx, params, x, x_dtype, rows, vals, idx, B, recon, want_bwd, dpre, last_activated, step_count, stats,
                          st);
 }

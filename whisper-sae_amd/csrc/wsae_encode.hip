@@ -850,7 +850,9 @@ extern "C" int wsae_encode_topk(wsae_ctx* ctx, const float* params, const void* 
     WSAE_REQUIRE(params && vals && idx, "wsae_encode_topk: null argument");
     hipStream_t st = (hipStream_t)stream;
     int32_t* fb = stats ? &stats->topk_fallback_rows : ctx->counters;
-    return wsae_internal_encode_topk(ctx, params, x, x_dtype, rows, B, vals, idx, step_count, fb, st);
+    rc = wsae_internal_encode_topk(ctx, params, x, x_dtype, rows, B, vals, idx, step_count, fb, st);
+    if (rc || !ctx->btk_k) return rc;
+    return wsae_internal_batch_topk(ctx, vals, B, ctx->btk_k, ctx->btk_mode, ctx->btk_state, st);  // (wsae_ctx_set_batch_topk)
 }
 
 extern "C" int wsae_densify(wsae_ctx* ctx, const float* vals, const int32_t* idx, int32_t B, float* hidden,

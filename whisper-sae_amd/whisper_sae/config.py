@@ -7,7 +7,9 @@ files stay valid:
 * ``sae.sparsity_weight``  -- L1 weight handed to ``ReLUSAE`` (the reference's ``create_sae`` drops
   it and silently uses 0.01, SURVEY.md row A13);
 * ``training.resample_dead_every`` / ``training.resample_batch_size`` -- the trainer defaults the
-  reference hard-codes in ``SAETrainer.__init__`` (training.py:41-42), exposed for YAML use.
+  reference hard-codes in ``SAETrainer.__init__`` (training.py:41-42), exposed for YAML use;
+* ``sae.activation: batchtopk`` with ``sae.batch_topk_max_k`` / ``sae.batch_topk_threshold_beta`` -- the BatchTopK SAE
+  the reference lists among its V2 requirements.
 """
 
 from __future__ import annotations
@@ -52,12 +54,26 @@ class SAEConfig(BaseModel):
     """Sparse-autoencoder architecture."""
 
     expansion_factor: int = Field(8, ge=4, le=32, description="hidden_dim = input_dim * expansion_factor")
-    activation: Literal["topk", "relu", "gelu"] = Field("topk")
+    activation: Literal["topk", "batchtopk", "relu", "gelu"] = Field("topk")
     k: int = Field(32, ge=1, description="active features per token (TopK)")
     normalize_decoder: bool = Field(True, description="keep decoder columns at unit L2 norm")
     dead_feature_threshold: int = Field(10_000, description="steps without firing before a feature counts as dead")
     dead_feature_resample: bool = Field(True, description="re-initialise dead features from high-error inputs")
     sparsity_weight: float = Field(0.01, ge=0, description="L1 weight of the ReLU SAE (ignored by TopK)")
+    batch_topk_max_k: Optional[int] = Field(None, ge=1, le=128,
+                                            description="BatchTopK only: most latents one row may keep (None = min(2 k, 128, "
+                                                        "hidden_dim))")
+    batch_topk_threshold_beta: float = Field(0.999, ge=0, lt=1,
+                                             description="BatchTopK only: EMA factor of the inference threshold")
+
+    @model_validator(mode="after")
+    def _check_batch_topk(self) -> "SAEConfig":
+        if self.activation == "batchtopk":
+            if self.k > 128:
+                raise ValueError(f"batchtopk needs k <= 128, got {self.k}")
+            if self.batch_topk_max_k is not None and self.batch_topk_max_k < self.k:
+                raise ValueError(f"batch_topk_max_k ({self.batch_topk_max_k}) must be >= k ({self.k})")
+        return self
 
     def get_hidden_dim(self, input_dim: int) -> int:
         return self.expansion_factor * input_dim

@@ -4,6 +4,8 @@ the reference's ``src/whisper_sae/sae/model.py``, with the arithmetic in ``libws
 * ``TopKSAE``  (reference model.py:26-257)  encode -> TopK -> sparse decode -> MSE, dead-feature
   tracking and resampling, all as HIP kernels working on a compact ``(values, indices)[B, k]`` code;
   the dense ``hidden [B, H]`` tensor of ``SAEOutput`` is materialised only for API callers.
+* ``BatchTopKSAE`` (not in the reference; its V2 requirements ask for it): the TopK path with a batch-wide
+  selection of the ``B * k`` largest activations and a learned inference threshold.
 * ``ReLUSAE``  (reference model.py:260-322).
 * ``create_sae`` (reference model.py:325-354), additionally forwarding ``config.sparsity_weight``.
 
@@ -79,6 +81,7 @@ class _TopKForward(torch.autograd.Function):
         last_ptr = module.feature_last_activated.data_ptr() if training else 0
         pk, xd = eng.pack.data_ptr(), _dtype_code(x2)
         N.check(lib.wsae_ctx_set_fired(handle, 0), "wsae_ctx_set_fired")  # the trainer's DDP clock exchange is per step
+        module._arm_selection(handle, "train" if training else "eval")
         # want_bwd: bit 0 = keep g / dpre for the weight gradients, bit 1 = also the fp32 g that dL/dx reads
         want = (1 if need_bwd else 0) | (2 if (need_bwd and ctx.needs_input_grad[0]) else 0)
         N.check(lib.wsae_encode_decode(handle, pk, x2.data_ptr(), xd, 0, B, vals.data_ptr(), idx.data_ptr(), step_ptr,
@@ -115,6 +118,7 @@ class _TopKForward(torch.autograd.Function):
             tmp_v = torch.empty_like(vals)
             tmp_i = torch.empty_like(idx)
             dpre = torch.empty_like(vals)
+            module._arm_selection(handle, None)  # (restaging only: the saved code is the one the forward selected)
             N.check(lib.wsae_encode_topk(handle, pk, x2.data_ptr(), xd, 0, B, tmp_v.data_ptr(), tmp_i.data_ptr(), 0,
                                          eng.stats.data_ptr(), st), "wsae_encode_topk")
             scratch = torch.zeros(N.STATS_WORDS, dtype=torch.int32, device=eng.device)
@@ -181,18 +185,19 @@ class TopKSAE(nn.Module):
         require_device_tensor(self.b_pre, "TopKSAE")
         if self.k > self.hidden_dim:
             raise ValueError(f"k={self.k} exceeds hidden_dim={self.hidden_dim}")
+        ek = self._engine_k()
         eng = self._engine
-        if eng is not None and eng.device == dev and eng.k == self.k:
+        if eng is not None and eng.device == dev and eng.k == ek:
             # fast path (every train step comes through here twice): nothing was re-pointed since the last full check
             ptrs = (self.encoder.weight.data_ptr(), self.decoder.weight.data_ptr(), self.encoder.bias.data_ptr(),
                     self.decoder.bias.data_ptr(), self.b_pre.data_ptr(), self.feature_last_activated.data_ptr(),
                     self.step_count.data_ptr())
             if ptrs == self._bound_ptrs:
                 return eng
-        if eng is None or eng.device != dev or eng.k != self.k:
+        if eng is None or eng.device != dev or eng.k != ek:
             if eng is not None:
                 eng.close()
-            eng = SAEEngine(dev, self.input_dim, self.hidden_dim, self.k)
+            eng = SAEEngine(dev, self.input_dim, self.hidden_dim, ek)
             self._engine = eng
         with torch.no_grad():
             for name, p in self._named_core_params().items():
@@ -209,6 +214,13 @@ class TopKSAE(nn.Module):
                             self.decoder.bias.data_ptr(), self.b_pre.data_ptr(), self.feature_last_activated.data_ptr(),
                             self.step_count.data_ptr())
         return eng
+
+    def _engine_k(self) -> int:
+        """Width of the compact code the kernels produce (the TopK k; BatchTopKSAE: its per-row cap)."""
+        return self.k
+
+    def _arm_selection(self, handle: int, mode: Optional[str]) -> None:
+        """Hook of BatchTopKSAE (sets the batch-wide selection of the ctx before an encode); plain TopK: nothing."""
 
     def param_token(self) -> tuple:
         """Changes whenever a parameter was re-pointed or modified in place through autograd-visible ops."""
@@ -232,6 +244,7 @@ class TopKSAE(nn.Module):
         B = x2.shape[0]
         prec = _precision_code(self.precision)
         handle = eng.prepare(prec, B, force=True)
+        self._arm_selection(handle, "select" if training else "eval")
         vals = torch.empty(B, eng.k, dtype=torch.float32, device=eng.device)
         idx = torch.empty(B, eng.k, dtype=torch.int32, device=eng.device)
         N.check(eng.lib.wsae_encode_topk(handle, eng.pack.data_ptr(), x2.data_ptr(), _dtype_code(x2), 0, B,
@@ -243,7 +256,7 @@ class TopKSAE(nn.Module):
     @torch.no_grad()
     def encode_compact(self, x: Tensor):
         """TopK code without the dense scatter: ``(values [B,k] f32 pre-activations, indices [B,k] i32)``."""
-        _, _, _, vals, idx = self._code(x, False)
+        _, _, _, vals, idx = self._code(x, self.training)
         return vals, idx
 
     @torch.no_grad()
@@ -264,7 +277,7 @@ class TopKSAE(nn.Module):
     @torch.no_grad()
     def encode(self, x: Tensor) -> Tensor:
         """Dense sparse code ``[.., H]`` with at most ``k`` non-zeros per row (reference model.py:98-118)."""
-        eng, handle, x2, vals, idx = self._code(x, False)
+        eng, handle, x2, vals, idx = self._code(x, self.training)
         hidden = torch.empty(x2.shape[0], eng.H, dtype=torch.float32, device=eng.device)
         N.check(eng.lib.wsae_densify(handle, vals.data_ptr(), idx.data_ptr(), x2.shape[0], hidden.data_ptr(),
                                      eng.stream()), "wsae_densify")
@@ -329,6 +342,7 @@ class TopKSAE(nn.Module):
         # (data parallel: this forward runs identically on every rank, so its clock stamps need no exchange - keep
         # them out of the indicator buffer that rides on the next gradient all-reduce)
         N.check(lib.wsae_ctx_set_fired(handle, 0), "wsae_ctx_set_fired")
+        self._arm_selection(handle, "select" if training else "eval")
         vals = torch.empty(Br, eng.k, dtype=torch.float32, device=eng.device)
         idx = torch.empty(Br, eng.k, dtype=torch.int32, device=eng.device)
         recon = torch.empty(Br, eng.D, dtype=torch.float32, device=eng.device)
@@ -355,6 +369,92 @@ class TopKSAE(nn.Module):
 
     def extra_repr(self) -> str:
         return f"input_dim={self.input_dim}, hidden_dim={self.hidden_dim}, k={self.k}"
+
+
+class BatchSelection(NamedTuple):
+    """Record of the last batch-wide selection of a ``BatchTopKSAE`` (``last_selection()``)."""
+
+    threshold: float      # t: the smallest kept value (theta in eval mode once trained); -1 when nothing was positive
+    saturated_rows: int   # rows whose max_k_per_row-th candidate was kept (0 when max_k_per_row = hidden_dim)
+    kept: int             # entries kept in the batch
+
+
+def default_max_k_per_row(k: int, hidden_dim: int) -> int:
+    """Per-row cap of ``BatchTopKSAE`` when none is given: ``min(2 k, 128, hidden_dim)`` (2 k keeps k = 32 on the
+    MFMA decode, which serves code widths up to 64)."""
+    return min(2 * int(k), 128, int(hidden_dim))
+
+
+class BatchTopKSAE(TopKSAE):
+    """BatchTopK sparse autoencoder (Bussmann, Leask & Nanda 2024).
+
+    Training mode keeps the ``B * k`` largest positive pre-activations of the whole batch instead of ``k`` per row,
+    with at most ``max_k_per_row`` per row (the candidates are the per-row TopK of that width); rows with more signal get
+    more latents.  Every training-mode ``forward`` moves the scalar ``threshold`` (a buffer, in the state dict) towards
+    the batch's cut ``t``: ``t`` itself the first time, then ``threshold_beta * threshold + (1 - threshold_beta) * t``.
+    Eval mode keeps the candidates above ``threshold`` (JumpReLU style, independent of the batch), or selects over the
+    batch while ``threshold`` is still -1 (never trained).  ``encode``, ``encode_compact`` and
+    ``resample_dead_features`` select the same way by ``self.training`` but leave ``threshold`` unchanged.  The
+    selection runs on the device between the TopK and the decode launches; the rest of the step is ``TopKSAE``'s.
+    """
+
+    def __init__(self, input_dim: int, hidden_dim: int, k: int = 32, max_k_per_row: Optional[int] = None,
+                 threshold_beta: float = 0.999, normalize_decoder: bool = True, dead_feature_threshold: int = 10_000,
+                 precision: Optional[str] = None):
+        super().__init__(input_dim, hidden_dim, k=k, normalize_decoder=normalize_decoder,
+                         dead_feature_threshold=dead_feature_threshold, precision=precision)
+        cap = default_max_k_per_row(k, hidden_dim) if max_k_per_row is None else int(max_k_per_row)
+        if not 1 <= k <= cap <= min(128, hidden_dim):
+            raise ValueError(f"BatchTopKSAE needs 1 <= k <= max_k_per_row <= min(128, hidden_dim), got k={k}, "
+                             f"max_k_per_row={cap}, hidden_dim={hidden_dim}")
+        if not 0.0 <= float(threshold_beta) < 1.0:
+            raise ValueError(f"threshold_beta must be in [0, 1), got {threshold_beta}")
+        self.max_k_per_row = cap
+        self.threshold_beta = float(threshold_beta)
+        self.register_buffer("threshold", torch.tensor(-1.0, dtype=torch.float32))
+        self._btk_state: Optional[Tensor] = None  # device record wsae_batch_topk_state; `threshold` is a view of word 0
+        self._btk_beta: Optional[float] = None
+
+    def _engine_k(self) -> int:
+        return self.max_k_per_row
+
+    def bind(self) -> SAEEngine:
+        eng = super().bind()
+        rec = self._btk_state
+        if rec is None or rec.device != eng.device or self.threshold.data_ptr() != rec.data_ptr():
+            rec = torch.zeros(N.BTK_STATE_WORDS, dtype=torch.int32, device=eng.device)
+            f = rec.view(torch.float32)
+            with torch.no_grad():
+                f[0].copy_(self.threshold.detach().reshape(()))
+                f[2].fill_(-1.0)
+            self._btk_state = rec
+            self.threshold = f[0]  # the buffer becomes a view of the record the kernels update
+            self._btk_beta = None
+        if self._btk_beta != self.threshold_beta:
+            rec.view(torch.float32)[1].fill_(self.threshold_beta)
+            self._btk_beta = self.threshold_beta
+        return eng
+
+    def _arm_selection(self, handle: int, mode: Optional[str]) -> None:
+        """mode: "train" (select, update the threshold), "select" (select only), "eval", or None (off)."""
+        if mode is None:
+            kb, code, rec = 0, N.BTK_TRAIN, 0
+        else:
+            kb, code = self.k, {"train": N.BTK_TRAIN, "eval": N.BTK_EVAL, "select": N.BTK_SELECT}[mode]
+            rec = self._btk_state.data_ptr()
+        N.check(self._engine.lib.wsae_ctx_set_batch_topk(handle, kb, code, rec), "wsae_ctx_set_batch_topk")
+
+    def last_selection(self) -> BatchSelection:
+        """(t, saturated rows, kept entries) of the last selection on this module.  Read from the device record only
+        when called (one sync then); the selection itself never waits for the host."""
+        if self._btk_state is None:
+            return BatchSelection(-1.0, 0, 0)
+        rec = self._btk_state.cpu()
+        return BatchSelection(float(rec.view(torch.float32)[2]), int(rec[3]), int(rec[4]))
+
+    def extra_repr(self) -> str:
+        return (f"input_dim={self.input_dim}, hidden_dim={self.hidden_dim}, k={self.k}, "
+                f"max_k_per_row={self.max_k_per_row}, threshold_beta={self.threshold_beta}")
 
 
 class _ReLUForward(torch.autograd.Function):
@@ -496,6 +596,11 @@ class ReLUSAE(nn.Module):
 def create_sae(config: SAEConfig, input_dim: int) -> nn.Module:
     """Build the SAE a config describes (reference model.py:325-354)."""
     hidden_dim = config.get_hidden_dim(input_dim)
+    if config.activation == "batchtopk":
+        return BatchTopKSAE(input_dim=input_dim, hidden_dim=hidden_dim, k=config.k,
+                            max_k_per_row=config.batch_topk_max_k, threshold_beta=config.batch_topk_threshold_beta,
+                            normalize_decoder=config.normalize_decoder,
+                            dead_feature_threshold=config.dead_feature_threshold)
     if config.activation == "topk":
         return TopKSAE(input_dim=input_dim, hidden_dim=hidden_dim, k=config.k,
                        normalize_decoder=config.normalize_decoder,

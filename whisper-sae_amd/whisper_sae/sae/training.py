@@ -1,7 +1,8 @@
 """``SAETrainer`` for MI355X -- the reference's trainer surface (src/whisper_sae/sae/training.py)
 on top of the fused HIP train step.
 
-One ``train_step`` = stage batch -> encode GEMM (MFMA) -> [TopK + sparse decode + MSE + dpre] (MFMA, one launch) ->
+One ``train_step`` = stage batch -> encode GEMM (MFMA) -> [TopK + sparse decode + MSE + dpre] (MFMA, one launch;
+``BatchTopKSAE``: the batch-wide selection between the TopK and the decode) ->
 weight-gradient GEMMs (MFMA) -> [RCCL all-reduce under torch.distributed] -> clip + AdamW + decoder
 renorm -> dead-feature scan, all enqueued on the current HIP stream without a host sync.  The
 per-step scalars are written by the kernels into a device record and copied asynchronously to
@@ -34,7 +35,7 @@ from .. import _native as N
 from ..config import TrainingConfig
 from ..distributed import WireExchange, barrier, rank_and_world, sync_gradients, world
 from .engine import _dtype_code, require_device_tensor
-from .model import relu_fp8_flag
+from .model import BatchTopKSAE, relu_fp8_flag
 from .optim import FusedAdamW
 
 
@@ -276,7 +277,13 @@ class SAETrainer:
         stats = chunk.dev.data_ptr() + slot * N.STATS_WORDS * 4  # this step's record: written in place, never copied
         step_ptr = model.step_count.data_ptr()
         ddp = world()[1] > 1
+        if ddp and isinstance(model, BatchTopKSAE):
+            raise N.WsaeError("BatchTopKSAE does not train data-parallel in this build: the batch-wide threshold would need "
+                              "a cross-rank selection (DESIGN.md section 10); train it on one GPU")
         N.check(lib.wsae_ctx_set_fired(handle, opt.fired.data_ptr() if ddp else 0), "wsae_ctx_set_fired")
+        arm = getattr(model, "_arm_selection", None)
+        if arm is not None:  # BatchTopKSAE: the batch-wide selection between the TopK and the decode (TopKSAE: no-op)
+            arm(handle, "train")
         # stage + encoder GEMM, then TopK + sparse decode + loss + dpre (one launch where the shape allows)
         N.check(lib.wsae_encode_decode(handle, pk, x.data_ptr(), xd, rp, B, w["vals"].data_ptr(), w["idx"].data_ptr(),
                                        step_ptr, 0, 1, w["dpre"].data_ptr(), model.feature_last_activated.data_ptr(),
