@@ -346,6 +346,34 @@ int wsae_ring_sample(wsae_ring* ring, uint64_t seed, int64_t epoch, int64_t offs
 /* fill with deterministic synthetic activations ~N(0,1) (bench / tests) */
 int wsae_ring_fill_synthetic(wsae_ring* ring, uint64_t seed, int64_t n_rows, void* stream);
 
+/* ---- causal feature interventions (row N5) ------------------------------------------------
+ * The consumer on the other side of the hooks: a block's output h [n_rows, dim] goes through the component's final
+ * LayerNorm (wsae_layernorm_rows: the row LayerNorm of wsae_ring_push_layernorm to a plain buffer dst [n_rows, dim] of
+ * dst_dtype), the SAE's compact code of it is edited, and the edit is written back into h in the model's own
+ * coordinates (wsae_intervene).  Per row, with mu and sigma = sqrt(var + eps) of h frozen, a = LN(h), (v_j, i_j) the
+ * row's code, act_j = max(v_j, 0):
+ *   act'_j = scale[i_j] * act_j, or c_f where i_j is a forced feature f; rows with row_mask[r] == 0 keep act'_j = act_j
+ *            and take no forced term (row_mask NULL = every row; scale NULL = all ones);
+ *   WSAE_IV_KEEP_ERROR  h' = h + sigma * (sum_j (act'_j - act_j) W_dT[i_j,:] + sum_{forced f not in the code} c_f W_dT[f,:]) / gamma
+ *   WSAE_IV_REPLACE     h' = mu + sigma * (b_d + b_pre + sum_j act'_j W_dT[i_j,:] + the same forced terms - beta) / gamma
+ * gamma == NULL: no norm (a = h, h' = h + delta or the edited reconstruction itself).  Terms with a zero weight are
+ * skipped; the others accumulate in fp32 in ascending j, forced terms after them in list order, over the decoder rows
+ * the ctx's decode reads (fp32 pack rows in FP32 mode, the bf16 shadow in BF16 mode: wsae_prepare first) - a fixed
+ * order, two runs are bit-identical.  A KEEP_ERROR row without a non-zero term is not stored (out == h) or copied
+ * (out != h): the identity edit leaves h bit-identical.  vals / idx: [n_rows, ctx k] as wsae_encode_topk wrote them;
+ * n_force <= WSAE_IV_MAX_FORCE; out may equal h (then out_dtype == h_dtype); changed_rows (nullable, device int32)
+ * receives the number of rows written with an edit (every row in REPLACE mode). */
+#define WSAE_IV_KEEP_ERROR 0
+#define WSAE_IV_REPLACE 1
+#define WSAE_IV_MAX_FORCE 64
+int wsae_layernorm_rows(const void* src, int32_t src_dtype, int64_t n_rows, int32_t dim, const float* gamma,
+                        const float* beta, float eps, void* dst, int32_t dst_dtype, void* stream);
+int wsae_intervene(wsae_ctx* ctx, const float* params, const void* h, int32_t h_dtype, int64_t n_rows,
+                   const float* vals, const int32_t* idx, const float* gamma, const float* beta, float eps,
+                   const float* scale, const int32_t* force_idx, const float* force_val, int32_t n_force,
+                   const uint8_t* row_mask, int32_t mode, void* out, int32_t out_dtype, int32_t* changed_rows,
+                   void* stream);
+
 /* ---- in-library kernel timing (bench.py's roofline leg) ----------------------------------------
  * When enabled for a kernel id, every launch of that kernel on this ctx is bracketed by a pair of
  * HIP events recorded on the launch stream (up to max_samples launches, then recording stops).

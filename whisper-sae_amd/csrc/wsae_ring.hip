@@ -5,6 +5,7 @@
 #include <new>
 
 #include "wsae_common.h"
+#include "wsae_layernorm.h"
 
 struct wsae_ring {
     int device, dim, dtype;
@@ -102,22 +103,10 @@ __global__ void __launch_bounds__(256) ring_push_ln_kernel(const void* __restric
     const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= n_rows) return;
     float v[VPL];
-    float sum = 0.f;
-#pragma unroll
-    for (int i = 0; i < VPL; ++i) {
-        const int d = lane + 64 * i;
-        v[i] = 0.f;
-        if (d < dim) v[i] = SRC == WSAE_DT_F32 ? ((const float*)src)[r * dim + d] : (float)((const bf16_t*)src)[r * dim + d];
-        sum += v[i];
-    }
-    const float mean = wave_sum(sum) / (float)dim;
-    float sq = 0.f;
-#pragma unroll
-    for (int i = 0; i < VPL; ++i) {
-        const float c = lane + 64 * i < dim ? v[i] - mean : 0.f;
-        sq = fmaf(c, c, sq);
-    }
-    const float rstd = rsqrtf(wave_sum(sq) / (float)dim + eps);  // biased variance, as torch.nn.LayerNorm
+    const float sum = ln_row_load<SRC, VPL>(src, r, dim, lane, v);
+    float mean, var_eps;
+    ln_row_stats<VPL>(v, sum, dim, lane, eps, mean, var_eps);
+    const float rstd = rsqrtf(var_eps);
     const int64_t slot = (head + r) % cap;
 #pragma unroll
     for (int i = 0; i < VPL; ++i) {
@@ -159,6 +148,33 @@ extern "C" int wsae_ring_push_layernorm(wsae_ring* ring, const void* src, int32_
     WSAE_LAUNCH_CHECK();
     ring->head = (ring->head + n_rows) % ring->cap;
     ring->size = min(ring->cap, ring->size + n_rows);
+    return WSAE_OK;
+}
+
+// The same row LayerNorm to a plain buffer (row N5: the activations an intervention's encoder reads): the kernel above
+// with the ring's wrap-around switched off (head 0, capacity n_rows), nothing staged in between.
+extern "C" int wsae_layernorm_rows(const void* src, int32_t src_dtype, int64_t n_rows, int32_t dim, const float* gamma,
+                                   const float* beta, float eps, void* dst, int32_t dst_dtype, void* stream) {
+    WSAE_REQUIRE(src && dst && gamma && beta && n_rows >= 0, "wsae_layernorm_rows: bad argument");
+    WSAE_REQUIRE(src_dtype == WSAE_DT_F32 || src_dtype == WSAE_DT_BF16, "wsae_layernorm_rows: unknown source dtype %d", src_dtype);
+    WSAE_REQUIRE(dst_dtype == WSAE_DT_F32 || dst_dtype == WSAE_DT_BF16, "wsae_layernorm_rows: unknown destination dtype %d", dst_dtype);
+    WSAE_REQUIRE(dim >= 1 && dim <= 2048, "wsae_layernorm_rows: row width %d outside [1, 2048]", dim);
+    if (n_rows == 0) return WSAE_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned nb = (unsigned)ceil_div64(n_rows, 4);
+#define ROWS_LN(S, D_, V) ring_push_ln_kernel<S, D_, V><<<nb, 256, 0, st>>>(src, dst, n_rows, dim, 0, n_rows, gamma, beta, eps)
+#define ROWS_LN_V(S, D_)                         \
+    do {                                         \
+        if (dim <= 512) ROWS_LN(S, D_, 8);       \
+        else ROWS_LN(S, D_, 32);                 \
+    } while (0)
+    if (src_dtype == WSAE_DT_F32 && dst_dtype == WSAE_DT_F32) ROWS_LN_V(WSAE_DT_F32, WSAE_DT_F32);
+    else if (src_dtype == WSAE_DT_F32) ROWS_LN_V(WSAE_DT_F32, WSAE_DT_BF16);
+    else if (dst_dtype == WSAE_DT_F32) ROWS_LN_V(WSAE_DT_BF16, WSAE_DT_F32);
+    else ROWS_LN_V(WSAE_DT_BF16, WSAE_DT_BF16);
+#undef ROWS_LN_V
+#undef ROWS_LN
+    WSAE_LAUNCH_CHECK();
     return WSAE_OK;
 }
 

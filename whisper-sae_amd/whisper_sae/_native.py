@@ -17,6 +17,7 @@ PREC_BF16, PREC_FP32 = 0, 1
 DT_F32, DT_BF16 = 0, 1
 PART_ALL, PART_DECODER, PART_ENCODER = -1, 0, 1  # wsae_weight_grads_wire
 BTK_TRAIN, BTK_EVAL, BTK_SELECT = 0, 1, 2  # wsae_batch_topk_select / wsae_ctx_set_batch_topk
+IV_KEEP_ERROR, IV_REPLACE, IV_MAX_FORCE = 0, 1, 64  # wsae_intervene
 BTK_STATE_WORDS = 8  # wsae_batch_topk_state: threshold, beta, last_t (f32), saturated_rows, kept, 3 reserved (i32)
 
 
@@ -95,6 +96,9 @@ SIGNATURES = {
     "wsae_profile_read": (C.c_int, [_p, _i32, C.POINTER(_i32), C.POINTER(C.c_double)]),
     "wsae_batch_topk_select": (C.c_int, [_p, _p, _i32, _i32, _i32, _p, _p]),
     "wsae_ctx_set_batch_topk": (C.c_int, [_p, _i32, _i32, _p]),
+    "wsae_layernorm_rows": (C.c_int, [_p, _i32, _i64, _i32, _p, _p, _f32, _p, _i32, _p]),
+    "wsae_intervene": (C.c_int, [_p, _p, _p, _i32, _i64, _p, _p, _p, _p, _f32, _p, _p, _p, _i32, _p, _i32, _p, _i32, _p,
+                                 _p]),
     "wsae_relu_needs_hidden": (C.c_int, [_p, _i32]),
     "wsae_relu_forward": (C.c_int, [_p, _p, _p, _i32, _p, _i32, _f32, _p, _p, _p, _p, _p]),
     "wsae_relu_backward": (C.c_int, [_p, _p, _p, _i32, _p, _i32, _f32, _p, _p, _p, _p]),
