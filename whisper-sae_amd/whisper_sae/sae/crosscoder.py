@@ -17,7 +17,8 @@ A TopK crosscoder IS a TopK SAE on the concatenated layers.  With ``x = [acts_l0
   ``g = 2 r / (B d_model)``) compute exactly that.
 
 So ``forward`` is ``wsae_encode_topk`` -> ``wsae_decode_loss`` (-> ``wsae_weight_grads`` / ``wsae_input_grad`` in
-backward) on one ``[B, n_layers * d_model]`` tensor, through the same autograd node as the transcoders.  The engine
+backward) on one ``[B, n_layers * d_model]`` tensor, through the same autograd node as the transcoders and the SAEs
+(``_SparsePath`` in ``packed.py``; the ReLU variant below shares ``_ReLUPath`` there with ``ReLUSAE``).  The engine
 limits apply to the concatenated width: ``n_layers * d_model <= 2048`` (Whisper-tiny x 4 layers = 1536, -base x 4 =
 2048), ``k <= 128``.
 
@@ -38,10 +39,9 @@ import torch
 from torch import Tensor, nn
 
 from .. import _native as N
-from .engine import SAEEngine, require_device_tensor
-from .model import _precision_code
-from .engine import _dtype_code
-from .transcoder import _SparsePath, _TranscoderBase, _as_rows
+from .engine import require_device_tensor
+from .packed import WeightedL1, _precision_code, _ReLUPath
+from .transcoder import _TranscoderBase
 
 
 class CrosscoderOutput(NamedTuple):
@@ -56,82 +56,6 @@ class CrosscoderOutput(NamedTuple):
     per_layer_loss: Dict[int, Tensor]
 
 
-class _ReLUCrossPath(torch.autograd.Function):
-    """wsae_relu_forward (-> wsae_relu_backward) on the concatenated layers with the decoder norms as per-feature L1
-    weights; gradients of ``loss`` with respect to the four parameters (the norm term of ``W_dec`` included)."""
-
-    @staticmethod
-    def forward(ctx, xc, w_e, b_e, w_d, b_d, module, prec):
-        eng: SAEEngine = module._engine
-        x2 = _as_rows(xc, module.input_dim, eng.D)
-        B = x2.shape[0]
-        handle = eng.prepare(prec, B, force=True)
-        eng.reserve_relu(handle)
-        lib, st = eng.lib, eng.stream()
-        norms = module.get_decoder_norms().detach().float().contiguous()
-        lam = float(module.sparsity_weight)
-        N.check(lib.wsae_ctx_set_relu_fp8(handle, 0), "wsae_ctx_set_relu_fp8")
-        N.check(lib.wsae_ctx_set_loss_cols(handle, module.d_model), "wsae_ctx_set_loss_cols")
-        N.check(lib.wsae_ctx_set_relu_l1_weights(handle, norms.data_ptr()), "wsae_ctx_set_relu_l1_weights")
-        hidden = torch.empty(B, eng.H, dtype=torch.float32, device=eng.device)
-        recon = torch.empty(B, eng.D, dtype=torch.float32, device=eng.device)
-        wmean = torch.empty((), dtype=torch.float32, device=eng.device)  # sum_b sum_s n_s |h| / (B H)
-        try:
-            N.check(lib.wsae_relu_forward(handle, eng.pack.data_ptr(), x2.data_ptr(), _dtype_code(x2), 0, B, lam * eng.H,
-                                          hidden.data_ptr(), recon.data_ptr(), eng.stats.data_ptr(), wmean.data_ptr(), st),
-                    "wsae_relu_forward")
-        finally:  # the weights are this call's: leave the ctx as the ReLU SAE expects it
-            lib.wsae_ctx_set_relu_l1_weights(handle, 0)
-            lib.wsae_ctx_set_loss_cols(handle, eng.D)
-        sf = eng.stats_f32()
-        loss, l0 = sf[0].clone(), sf[1].clone()
-        sparsity = wmean * float(eng.H)  # mean_b sum_s n_s |h_bs|  (reference crosscoder.py:217)
-        eng.generation += 1
-        ctx.module, ctx.prec, ctx.gen, ctx.B, ctx.lam = module, prec, eng.generation, B, lam
-        ctx.save_for_backward(x2, hidden, recon, norms)
-        ctx.set_materialize_grads(False)
-        recon_out = recon[:, :module.input_dim]
-        ctx.mark_non_differentiable(recon_out, hidden, sparsity, l0)
-        return recon_out, hidden, loss, sparsity, l0
-
-    @staticmethod
-    def backward(ctx, g_recon, g_hidden, g_loss, g_sparsity, g_l0):
-        if g_loss is None:
-            return (None,) * 7
-        module, prec, B, lam = ctx.module, ctx.prec, ctx.B, ctx.lam
-        eng: SAEEngine = module._engine
-        x2, hidden, recon, norms = ctx.saved_tensors
-        handle = eng.prepare(prec, B, force=True)
-        eng.reserve_relu(handle)
-        lib, st, pk, xd = eng.lib, eng.stream(), eng.pack.data_ptr(), _dtype_code(x2)
-        N.check(lib.wsae_ctx_set_relu_fp8(handle, 0), "wsae_ctx_set_relu_fp8")
-        N.check(lib.wsae_ctx_set_loss_cols(handle, module.d_model), "wsae_ctx_set_loss_cols")
-        N.check(lib.wsae_ctx_set_relu_l1_weights(handle, norms.data_ptr()), "wsae_ctx_set_relu_l1_weights")
-        grads = torch.empty(eng.P, dtype=torch.float32, device=eng.device)
-        try:
-            if eng.generation != ctx.gen:  # another call reused the ctx workspace since: restage this batch
-                h2, r2 = torch.empty_like(hidden), torch.empty_like(recon)
-                N.check(lib.wsae_relu_forward(handle, pk, x2.data_ptr(), xd, 0, B, lam * eng.H, h2.data_ptr(), r2.data_ptr(), 0, 0,
-                                              st), "wsae_relu_forward")
-                eng.generation += 1
-            N.check(lib.wsae_relu_backward(handle, pk, x2.data_ptr(), xd, 0, B, lam * eng.H, hidden.data_ptr(),
-                                           recon.data_ptr(), grads.data_ptr(), st), "wsae_relu_backward")
-        finally:
-            lib.wsae_ctx_set_relu_l1_weights(handle, 0)
-            lib.wsae_ctx_set_loss_cols(handle, eng.D)
-        need = ctx.needs_input_grad
-        if need[3] and lam != 0.0:
-            # d/dW_dec of lam * mean_b sum_s |h_bs| n_s through n_s = ||W_dec[s]||:  lam * mean_b|h_bs| * W_dec[s] / n_s
-            col = hidden.sum(dim=0) * (lam / B)                       # hidden >= 0
-            wd = module._sliced("decoder.weight").detach().reshape(module.d_sae, -1)
-            gview = eng.view("decoder.weight", grads)                # [Dp, H] view of the pack layout
-            gview[:module.input_dim, :].add_((wd * (col / norms.clamp_min(1e-30)).unsqueeze(1)).t())
-        grads.mul_(g_loss)
-        gv = lambda name, on: module._sliced(name, grads) if on else None  # noqa: E731
-        return (None, gv("encoder.weight", need[1]), gv("encoder.bias", need[2]), gv("decoder.weight", need[3]),
-                gv("decoder.bias", need[4]), None, None)
-
-
 class CrossLayerCrosscoder(_TranscoderBase):
     """Shared sparse code over several layers (reference crosscoder.py:38-283): parameters ``W_enc [n_layers, d_model,
     d_sae]``, ``b_enc [d_sae]``, ``W_dec [d_sae, n_layers, d_model]``, ``b_dec [n_layers, d_model]``."""
@@ -139,20 +63,13 @@ class CrossLayerCrosscoder(_TranscoderBase):
     def __init__(self, d_model: int, n_layers: int, d_sae: int, layer_indices: Optional[List[int]] = None,
                  activation: str = "relu", sparsity_weight: float = 0.01, normalize_decoder: bool = True,
                  dead_feature_threshold: int = 10_000, precision: Optional[str] = None):
-        nn.Module.__init__(self)
+        # the engine works on the concatenated layers; k: engine shape for decode(), the TopK subclass sets the real one
+        super().__init__(n_layers * d_model, n_layers * d_model, d_sae, min(32, d_sae), normalize_decoder,
+                         dead_feature_threshold, precision)
         self.d_model, self.n_layers, self.d_sae = d_model, n_layers, d_sae
         self.layer_indices = layer_indices or list(range(n_layers))
         self.activation = activation
         self.sparsity_weight = sparsity_weight
-        self.normalize_decoder = normalize_decoder
-        self.dead_feature_threshold = dead_feature_threshold
-        self.precision = precision
-        # the names the shared transcoder machinery works with
-        self.input_dim = self.output_dim = n_layers * d_model
-        self.hidden_dim = d_sae
-        self.k = min(32, d_sae)  # engine shape for decode(); the TopK subclass sets the real k
-        self._engine: Optional[SAEEngine] = None
-        self._last_code = None
         # same creation order (and RNG draw) as the reference (:88-99)
         self.W_enc = nn.Parameter(torch.empty(n_layers, d_model, d_sae))
         self.b_enc = nn.Parameter(torch.zeros(d_sae))
@@ -230,9 +147,24 @@ class CrossLayerCrosscoder(_TranscoderBase):
         if self.activation != "relu":
             raise ValueError(f"Unknown activation: {self.activation}")  # as the reference (crosscoder.py:167)
         self._check_width()
-        self.bind()
-        return _ReLUCrossPath.apply(xc, self.W_enc, self.b_enc, self.W_dec, self.b_dec, self,
-                                    _precision_code(self.precision))
+        eng = self.bind()
+        lam = float(self.sparsity_weight)
+        l1 = WeightedL1(self.get_decoder_norms().detach().float().contiguous(), self.d_model, lam)
+        recon, hidden, loss, wmean, l0 = _ReLUPath.apply(xc, self, _precision_code(self.precision), lam * eng.H, 0, l1,
+                                                         *self._named_core_params().values())
+        # wmean = sum_b sum_s n_s |h| / (B H)  ->  mean_b sum_s n_s |h_bs|  (reference crosscoder.py:217)
+        return recon, hidden, loss, wmean * float(eng.H), l0
+
+    def _l1_weight_grads(self, grads: Tensor, hidden: Tensor, l1: WeightedL1) -> None:
+        """Adds to the flat gradient buffer what the decoder norms contribute as L1 weights: d/dW_dec of ``lam * mean_b
+        sum_s |h_bs| n_s`` through ``n_s = ||W_dec[s]||``  =  ``lam * mean_b|h_bs| * W_dec[s] / n_s``."""
+        lam = l1.sparsity_weight
+        if lam == 0.0:
+            return
+        col = hidden.sum(dim=0) * (lam / hidden.shape[0])                 # hidden >= 0
+        wd = self._sliced("decoder.weight").detach().reshape(self.d_sae, -1)
+        gview = self._engine.view("decoder.weight", grads)               # [Dp, H] view of the pack layout
+        gview[:self.input_dim, :].add_((wd * (col / l1.weights.clamp_min(1e-30)).unsqueeze(1)).t())
 
     @torch.no_grad()
     def encode(self, layer_activations: Dict[int, Tensor]) -> Tensor:
@@ -243,7 +175,7 @@ class CrossLayerCrosscoder(_TranscoderBase):
     def decode(self, hidden: Tensor) -> Dict[int, Tensor]:
         """Per-layer reconstructions of any dense code (reference crosscoder.py:171-186)."""
         self._check_width()
-        return self._split(_TranscoderBase.decode(self, hidden))
+        return self._split(super().decode(hidden))
 
     def forward(self, layer_activations: Dict[int, Tensor]) -> CrosscoderOutput:
         """Reference crosscoder.py:188-235: sum of per-layer MSEs + ``sparsity_weight`` x decoder-norm-weighted L1."""
@@ -295,9 +227,7 @@ class TopKCrossLayerCrosscoder(CrossLayerCrosscoder):
         and reconstructions are read-outs.  In training mode also advances the dead-feature clock."""
         self._check_width()
         xc = self._gather(layer_activations, need_all=True)
-        self.bind()
-        recon, hidden, loss, l0 = _SparsePath.apply(xc, xc, self.W_enc, self.b_enc, self.W_dec, self.b_dec, self,
-                                                    _precision_code(self.precision))
+        recon, hidden, loss, l0 = self._sparse(xc, xc)
         with torch.no_grad():
             err = (recon - xc.detach().float()).square_().view(-1, self.n_layers, self.d_model).mean(dim=(0, 2))
         per_layer = {li: err[i] for i, li in enumerate(self.layer_indices)}
