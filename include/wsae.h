@@ -374,6 +374,39 @@ int wsae_intervene(wsae_ctx* ctx, const float* params, const void* h, int32_t h_
                    const uint8_t* row_mask, int32_t mode, void* out, int32_t out_dtype, int32_t* changed_rows,
                    void* stream);
 
+/* ---- feature attribution (attribution patching) ---------------------------------------------
+ * The first-order effect on a scalar metric m of the edit wsae_intervene applies in WSAE_IV_KEEP_ERROR mode, for every
+ * code entry and per feature, from one gradient: grad_h = G = dm/dh' [n_rows, dim] with respect to the tapped block's
+ * output on the clean run.  Same setting as wsae_intervene: h [n_rows, dim], (gamma, eps) of the component's final
+ * LayerNorm, (v_j, i_j) the row's code of a = LN(h).  Since h' = h + sigma (sum_j (act'_j - act_j) W_dT[i_j,:]) / gamma
+ * with mu and sigma frozen, per row r and code entry j:
+ *   act_j   = max(v_j, 0)
+ *   w_j     = (scale[i_j] - 1) * act_j   (scale NULL: ablate everything, w_j = -act_j; rows with row_mask[r] == 0 and
+ *                                         entries whose index is outside [0, hidden_dim): w_j = 0)
+ *   s_j     = sum_d (G[r,d] / gamma_d) * W_dT[i_j, d]          (gamma NULL: G[r,d] itself, and sigma = 1)
+ *   attr_rj = sigma_r * w_j * s_j,       sigma_r = sqrt(var_r + eps), biased variance (the statistics of wsae_intervene)
+ * This is the exact first-order term of the intervention, which freezes each row's statistics; it is not the derivative
+ * through a differentiated LayerNorm.  Forced (clamped) features and WSAE_IV_REPLACE are out of scope.  W_dT: the
+ * decoder rows the ctx's decode reads (fp32 pack rows in FP32 mode, the bf16 shadow in BF16 mode: wsae_prepare first).
+ * u_d = G_d / gamma_d is rounded once, s_j accumulates in fp32 (fmaf), attr = (sigma * w_j) * s_j.  An entry with
+ * w_j == 0 gets attr_rj = 0.0f exactly and its decoder row is not read.
+ * Inputs are expected to be finite.  A non-finite attr_rj anywhere in the call (an Inf or NaN gradient, an overflow) is
+ * propagated, not hidden: attr carries it, feat_sum and feat_abs are NaN for every feature, feat_rows stays exact.
+ * Per feature f over the whole call (each output nullable; any of them needs the workspace):
+ *   feat_sum[f] = sum of attr_rj over the entries with i_j == f, feat_abs[f] the same over |attr_rj|,
+ *   feat_rows[f] = number of entries with i_j == f and w_j != 0.
+ * The sums are exact fixed point: A = max |attr_rj| of the call, A < 2^e, q = 2^(e - 36); every entry adds the integer
+ * rint(attr_rj / q) to a 64-bit accumulator and the result is float(acc * q), rounded once (error <= q / 2 per entry
+ * plus that rounding; A == 0: zeros).  n_rows * k <= 2^26, so the accumulators cannot overflow.  No float atomics: two
+ * calls give the same bits, attr of a row depends on that row alone, and feat_sum / feat_abs depend neither on the
+ * launch geometry nor on the order of the rows.  h, grad_h: f32 or bf16; vals / idx / attr: [n_rows, ctx k];
+ * workspace: wsae_attribute_workspace_bytes(hidden_dim) bytes, 8-byte aligned, cleared inside the call. */
+int64_t wsae_attribute_workspace_bytes(int32_t hidden_dim);
+int wsae_attribute(wsae_ctx* ctx, const float* params, const void* h, int32_t h_dtype, const void* grad_h,
+                   int32_t grad_dtype, int64_t n_rows, const float* vals, const int32_t* idx, const float* gamma,
+                   float eps, const float* scale, const uint8_t* row_mask, float* attr, float* feat_sum, float* feat_abs,
+                   int32_t* feat_rows, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- in-library kernel timing (bench.py's roofline leg) ----------------------------------------
  * When enabled for a kernel id, every launch of that kernel on this ctx is bracketed by a pair of
  * HIP events recorded on the launch stream (up to max_samples launches, then recording stops).

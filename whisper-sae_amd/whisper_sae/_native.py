@@ -99,6 +99,9 @@ SIGNATURES = {
     "wsae_layernorm_rows": (C.c_int, [_p, _i32, _i64, _i32, _p, _p, _f32, _p, _i32, _p]),
     "wsae_intervene": (C.c_int, [_p, _p, _p, _i32, _i64, _p, _p, _p, _p, _f32, _p, _p, _p, _i32, _p, _i32, _p, _i32, _p,
                                  _p]),
+    "wsae_attribute_workspace_bytes": (_i64, [_i32]),
+    "wsae_attribute": (C.c_int, [_p, _p, _p, _i32, _p, _i32, _i64, _p, _p, _p, _f32, _p, _p, _p, _p, _p, _p, _p, _i64,
+                                 _p]),
     "wsae_relu_needs_hidden": (C.c_int, [_p, _i32]),
     "wsae_relu_forward": (C.c_int, [_p, _p, _p, _i32, _p, _i32, _f32, _p, _p, _p, _p, _p]),
     "wsae_relu_backward": (C.c_int, [_p, _p, _p, _i32, _p, _i32, _f32, _p, _p, _p, _p]),

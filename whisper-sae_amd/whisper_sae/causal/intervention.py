@@ -32,6 +32,56 @@ def _norm_parts(layer_norm) -> tuple:
     return weight, bias, float(eps)
 
 
+def _positions(positions: Optional[Iterable[int]]) -> Optional[list]:
+    if positions is None:
+        return None
+    out = sorted({int(p) for p in positions})
+    if out and out[0] < 0:
+        raise ValueError("positions are non-negative indices")
+    return out
+
+
+class _Operands:
+    """Device operands shared by the kernels that read hidden states through a LayerNorm (``SAEIntervention``,
+    ``SAEAttribution``): the norm's fp32 tensors and the row mask of ``positions``, each built once and cached."""
+
+    def __init__(self, positions: Optional[Iterable[int]] = None):
+        self.positions = _positions(positions)
+        self._norm_cache: dict = {}
+        self._mask_cache: dict = {}
+
+    def norm_tensors(self, layer_norm, device) -> tuple:
+        weight, bias, eps = _norm_parts(layer_norm)
+        key = (weight.data_ptr(), weight._version, bias.data_ptr(), bias._version, str(device))
+        have = self._norm_cache.get(key)
+        if have is None:
+            gamma = weight.detach().to(device=device, dtype=torch.float32).contiguous()
+            beta = bias.detach().to(device=device, dtype=torch.float32).contiguous()
+            if bool((gamma == 0).any()):
+                raise ValueError("the LayerNorm weight has a zero entry: its inverse does not exist there")
+            self._norm_cache.clear()
+            have = self._norm_cache[key] = (gamma, beta)
+        return have[0], have[1], eps
+
+    def row_mask(self, shape, device) -> Optional[Tensor]:
+        if self.positions is None:
+            return None
+        if len(shape) < 2:
+            raise ValueError("positions need hidden states with a time dimension ([.., T, D])")
+        key = (tuple(shape[:-1]), str(device))
+        mask = self._mask_cache.get(key)
+        if mask is None:
+            steps = shape[-2]
+            if self.positions and self.positions[-1] >= steps:
+                raise ValueError(f"position {self.positions[-1]} is outside the {steps} time steps of the hidden states")
+            line = torch.zeros(steps, dtype=torch.uint8)
+            line[self.positions] = 1
+            mask = line.expand(*shape[:-1]).reshape(-1).contiguous().to(device)
+            self._mask_cache.clear()
+            self._mask_cache[key] = mask
+        return mask
+
+
 class SAEIntervention:
     """Switch features of ``sae`` off, up or to a constant inside hidden states.
 
@@ -57,45 +107,17 @@ class SAEIntervention:
             raise TypeError("edit must be a FeatureEdit")
         self.layer_norm = layer_norm
         self.mode = mode
-        self.positions = None if positions is None else sorted({int(p) for p in positions})
-        if self.positions is not None and self.positions and self.positions[0] < 0:
-            raise ValueError("positions are non-negative indices")
-        self._norm_cache: dict = {}
-        self._mask_cache: dict = {}
+        self._ops = _Operands(positions)
+        self.positions = self._ops.positions
         self._changed: Optional[Tensor] = None
         self.last_code = None  # (vals, idx) of the last apply: the code the kernel was handed
 
     # -- operands --------------------------------------------------------------------------------
     def _norm_tensors(self, layer_norm, device) -> tuple:
-        weight, bias, eps = _norm_parts(layer_norm)
-        key = (weight.data_ptr(), weight._version, bias.data_ptr(), bias._version, str(device))
-        have = self._norm_cache.get(key)
-        if have is None:
-            gamma = weight.detach().to(device=device, dtype=torch.float32).contiguous()
-            beta = bias.detach().to(device=device, dtype=torch.float32).contiguous()
-            if bool((gamma == 0).any()):
-                raise ValueError("the LayerNorm weight has a zero entry: its inverse does not exist there")
-            self._norm_cache.clear()
-            have = self._norm_cache[key] = (gamma, beta)
-        return have[0], have[1], eps
+        return self._ops.norm_tensors(layer_norm, device)
 
     def _row_mask(self, shape, device) -> Optional[Tensor]:
-        if self.positions is None:
-            return None
-        if len(shape) < 2:
-            raise ValueError("positions need hidden states with a time dimension ([.., T, D])")
-        key = (tuple(shape[:-1]), str(device))
-        mask = self._mask_cache.get(key)
-        if mask is None:
-            steps = shape[-2]
-            if self.positions and self.positions[-1] >= steps:
-                raise ValueError(f"position {self.positions[-1]} is outside the {steps} time steps of the hidden states")
-            line = torch.zeros(steps, dtype=torch.uint8)
-            line[self.positions] = 1
-            mask = line.expand(*shape[:-1]).reshape(-1).contiguous().to(device)
-            self._mask_cache.clear()
-            self._mask_cache[key] = mask
-        return mask
+        return self._ops.row_mask(shape, device)
 
     # -- the intervention --------------------------------------------------------------------------
     @torch.no_grad()
