@@ -479,6 +479,34 @@ int wsae_relu_backward(wsae_ctx* ctx, const float* params, const void* x, int32_
                        const int32_t* rows, int32_t B, float sparsity_weight, const float* hidden,
                        const float* recon, float* grads, void* stream);
 
+/* ---- dictionary comparison: nearest rows of B for every row of A ---------------------------
+ * For every row i of A [rows_a, dim] the top_n most similar rows j of B [rows_b, dim], without the [rows_a, rows_b]
+ * similarity matrix ever existing in memory: a GEMM whose epilogue is the selection.  Ctx-free (two dictionaries of
+ * different hidden_dim cannot share a ctx).  A, B: fp32, row-major, leading dimensions lda, ldb >= dim in elements
+ * (multiples of 4; the pointers 16-byte aligned), so the W_e or W_dT rows of a pack, or one layer's column slice of a
+ * crosscoder's decoder rows, are passed in place.  dim: a multiple of 32, <= 2048.  rows_a, rows_b >= 1, any value;
+ * a column >= rows_b is never selected.  1 <= top_n <= WSAE_MATCH_MAX_N.  B may be A.
+ * Arithmetic.  WSAE_MATCH_COSINE: a^ = a * (1 / max(sqrt(sum_d a_d^2), 1e-12)), sum and scaling in fp32 (a zero row has
+ * similarity 0 to everything), b^ likewise, sim_ij = sum_d a^_id b^_jd.  WSAE_MATCH_DOT: the raw rows.
+ * WSAE_PREC_FP32: fp32 MFMA on the fp32 operands.  WSAE_PREC_BF16: the (normalised) operands are rounded once to bf16
+ * (nearest even), fp32 accumulate.  A first pass stages the normalised / converted operands in the workspace; the
+ * contraction reads the staged copies.  sim_ij depends on row i of A and row j of B alone: every pair is summed in the
+ * same K order (ascending K steps of the MFMA, dim rounded up with zeros in BF16 mode), whatever tile, column split or
+ * neighbours it has; two calls give the same bits.
+ * Selection.  Per row of A the top_n largest sim_ij, sorted by value descending, then index ascending (ties go to the
+ * lowest index); this order is total, so the result does not depend on the launch geometry.  exclude_self != 0 skips
+ * column j == i (B is A).  With fewer than top_n candidates the tail is idx = -1, val = -inf.  Inputs are expected to
+ * be finite.  No float atomics; the column splits hand their candidates to a merge launch through the workspace.
+ * workspace: wsae_match_workspace_bytes (-1 for invalid arguments) bytes of device scratch, 16-byte aligned: the two
+ * staged operands (rows rounded up to 128) and top_n (rounded up to 4, 8 or 16) candidates per row and column split. */
+#define WSAE_MATCH_COSINE 0
+#define WSAE_MATCH_DOT 1
+#define WSAE_MATCH_MAX_N 16
+int64_t wsae_match_workspace_bytes(int32_t rows_a, int32_t rows_b, int32_t dim, int32_t top_n, int32_t precision);
+int wsae_match_rows(const float* A, int32_t rows_a, int64_t lda, const float* B, int32_t rows_b, int64_t ldb,
+                    int32_t dim, int32_t metric, int32_t precision, int32_t top_n, int32_t exclude_self,
+                    float* out_val, int32_t* out_idx, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
