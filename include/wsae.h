@@ -507,6 +507,53 @@ int wsae_match_rows(const float* A, int32_t rows_a, int64_t lda, const float* B,
                     int32_t dim, int32_t metric, int32_t precision, int32_t top_n, int32_t exclude_self,
                     float* out_val, int32_t* out_idx, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- co-activation statistics: co-firing counts and top partners -------------------------------
+ * Over a stream of rows of two compact codes A [n_rows, k_a] and B [n_rows, k_b] (as wsae_encode_topk writes them; k_a
+ * and k_b independent, each in 1..WSAE_COACT_MAX_K), count for every pair (feature i of A, feature j of B) the rows on
+ * which both fire, then pick per feature of A the strongest partners under a normalised score.  Ctx-free; the caller's
+ * stream, no allocation, no host synchronisation, no float atomics.  All state is integer: the results are identical
+ * for any launch geometry, any order of the rows and any split of the rows over calls.
+ * State (caller-owned, zero-initialised device memory): counts int32 [a_rows, ldc] (ldc >= hidden_b; columns from
+ * hidden_b on are never touched), fire_a int32 [hidden_a], fire_b int32 [hidden_b] (nullable in the update),
+ * total_rows int64 [1].
+ * wsae_coact_update.  An entry is active iff v > 0 and 0 <= idx < hidden (masked BatchTopK entries carry v = 0; an
+ * index outside the range is ignored).  A row with row_mask[r] == 0 contributes nothing (row_mask NULL: every row
+ * does).  Per contributing row: total_rows += 1; fire_a[i] += 1 per active entry of A, whatever the window;
+ * fire_b[j] += 1 per active entry of B; counts[i - a_lo][j] += 1 for every pair of an active entry of A with
+ * a_lo <= i < a_lo + a_rows and an active entry of B (a repeated index counts once per occurrence).  vals_b / idx_b
+ * may be the buffers of A: the table is then symmetric and its diagonal equals fire_a.  The window (a_lo, a_rows) lets
+ * a large pair of dictionaries be processed in passes over row ranges of the table.  0 <= n_rows <= 2^31 - 1 per call;
+ * keeping the cumulative total below 2^31 is the caller's job.
+ * wsae_coact_top.  For every window row r (i = a_lo + r; c = counts[r][j], n = fire_a[i], m = fire_b[j],
+ * N = *total_rows, read on the device) the top_n <= WSAE_MATCH_MAX_N best columns; the score matrix is never written.
+ * Scores are fp64 from the integers with correctly rounded IEEE operations, rounded once to fp32:
+ *   WSAE_COACT_COUNT    c
+ *   WSAE_COACT_COND     c / n                      (0 if n == 0)
+ *   WSAE_COACT_JACCARD  c / (n + m - c)            (denominator in int64; 0 if it is 0)
+ *   WSAE_COACT_PHI      double(N c - n m) / (sqrt(double(n (N - n))) * sqrt(double(m (N - m))))
+ *                                                  (products in int64; 0 if either product under a root is 0)
+ * A column is a candidate iff j < hidden_b, c >= min_count (min_count >= 0) and, with exclude_self != 0, j != i.
+ * Order: fp32 value descending, then index ascending (total, so independent of geometry).  With fewer than top_n
+ * candidates the tail is val = -inf, idx = -1, cnt = 0.  out_cnt (nullable) receives c of each selected pair; fire_b
+ * may be NULL for the COUNT and COND metrics.  Both workspace queries return 0 (neither call needs scratch; workspace
+ * may be NULL) and -1 for invalid arguments. */
+#define WSAE_COACT_COUNT 0
+#define WSAE_COACT_COND 1
+#define WSAE_COACT_JACCARD 2
+#define WSAE_COACT_PHI 3
+#define WSAE_COACT_MAX_K 128
+int64_t wsae_coact_workspace_bytes(int64_t n_rows, int32_t k_a, int32_t hidden_a, int32_t k_b, int32_t hidden_b,
+                                   int32_t a_lo, int32_t a_rows);
+int wsae_coact_update(const float* vals_a, const int32_t* idx_a, int32_t k_a, int32_t hidden_a, const float* vals_b,
+                      const int32_t* idx_b, int32_t k_b, int32_t hidden_b, int64_t n_rows, const uint8_t* row_mask,
+                      int32_t a_lo, int32_t a_rows, int32_t* counts, int64_t ldc, int32_t* fire_a, int32_t* fire_b,
+                      int64_t* total_rows, void* workspace, int64_t workspace_bytes, void* stream);
+int64_t wsae_coact_top_workspace_bytes(int32_t a_lo, int32_t a_rows, int32_t hidden_b, int32_t top_n);
+int wsae_coact_top(const int32_t* counts, int64_t ldc, int32_t a_lo, int32_t a_rows, int32_t hidden_b,
+                   const int32_t* fire_a, const int32_t* fire_b, const int64_t* total_rows, int32_t metric,
+                   int32_t min_count, int32_t exclude_self, int32_t top_n, float* out_val, int32_t* out_idx,
+                   int32_t* out_cnt, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,10 +18,10 @@
 #include <math.h>
 
 #include "wsae_mfma.h"
+#include "wsae_toplist.h"
 
 namespace {
 
-constexpr int MT_EMPTY = 0x7fffffff;      // index of an unused list slot (value -inf); no real column reaches it
 constexpr int MT_TARGET_BLOCKS = 512;     // column splits are added until the grid has about two blocks per CU
 
 struct MatchPlan {
@@ -103,22 +103,6 @@ __global__ __launch_bounds__(256) void match_stage_kernel(const float* __restric
             }
         }
         mt_store4(d + 4 * c, v);
-    }
-}
-
-// (v, i) into the list sorted by value descending, then index ascending; the last element falls out.  All indexing
-// is static: the list stays in registers.
-template <int NB>
-__device__ __forceinline__ void mt_insert(float (&lv)[NB], int (&li)[NB], float v, int i) {
-#pragma unroll
-    for (int p = 0; p < NB; ++p) {
-        const float tv = lv[p];
-        const int ti = li[p];
-        const bool b = v > tv || (v == tv && i < ti);
-        lv[p] = b ? v : tv;
-        li[p] = b ? i : ti;
-        v = b ? tv : v;
-        i = b ? ti : i;
     }
 }
 

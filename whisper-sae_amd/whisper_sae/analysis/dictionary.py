@@ -7,7 +7,7 @@ never materialised.  The rows of a bound module are read in place from its param
 decoder, ``W_e`` rows for the encoder, one layer's column slice for a crosscoder), with the pack's row stride as the
 leading dimension.  The reductions over the resulting ``[H]`` vectors are plain torch.
 
-Out of scope: optimal one-to-one assignment (Hungarian), activation-based (co-firing) similarity, a feature -> token
+Out of scope: optimal one-to-one assignment (Hungarian), a feature -> token
 "logit lens" on the dot metric (the kernel takes any ``rows_b``; the Whisper-side glue is not here), fp8 operands.
 """
 
