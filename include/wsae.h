@@ -554,6 +554,51 @@ int wsae_coact_top(const int32_t* counts, int64_t ldc, int32_t a_lo, int32_t a_r
                    int32_t min_count, int32_t exclude_self, int32_t top_n, float* out_val, int32_t* out_idx,
                    int32_t* out_cnt, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- group effect sizes: utterance pooling and bootstrap Cohen's d ------------------------------
+ * Which features separate two groups of utterances, and how surely.  Ctx-free; the caller's stream, no allocation, no
+ * host synchronisation, no float atomics; argument errors are found on the host before any HIP call.
+ * wsae_pool_update.  Segment pooling of a compact code vals / idx [n_rows, k] (as wsae_encode_topk writes them,
+ * 1 <= k <= WSAE_POOL_MAX_K).  seg int32 [n_rows] names the segment (utterance) of each row; a row with seg < 0 or
+ * seg >= n_seg contributes nothing (padding frames).  The remaining values are expected to be non-decreasing within a
+ * call (the frames of an utterance arrive together); where they are not, the result is the same and the call slower.
+ * State (caller-owned, zero-initialised device memory): pooled_sum fp32 [n_seg, ld], pooled_cnt int32 [n_seg, ld]
+ * (nullable), seg_rows int32 [n_seg]; ld >= f_cols, columns from f_cols on are never touched.  An entry is active iff
+ * v > 0 and 0 <= idx < hidden (the rule of wsae_coact_update).  Per contributing row seg_rows[s] += 1; per active entry
+ * with f_lo <= idx < f_lo + f_cols: pooled_sum[s][idx - f_lo] += v and pooled_cnt[s][idx - f_lo] += 1.
+ * pooled_sum[s][f] is the fp32 sum in ascending row order (within a row: ascending entry position, which only matters
+ * for an index repeated within a row), starting from the value already stored: a segment split over two calls, or any
+ * launch geometry, gives the same bits, and sequential float32 adds reproduce them.  0 <= n_rows <= 2^31 - 1 per call.
+ * Workspace: wsae_pool_workspace_bytes (8 n_seg bytes: the first and last row of each segment; -1 for invalid
+ * arguments), contents arbitrary on entry.
+ * wsae_group_effect.  Effect sizes of two groups of segments in fp64.  X fp32 [n_seg, ld] (the pooled_sum state, or any
+ * dense per-utterance matrix), div int32 [n_seg] (nullable = 1): x_sf = double(X[s][f]) / div[s], a segment with
+ * div[s] <= 0 is left out.  group int32 [n_seg]: 0 = group a, 1 = group b, anything else is ignored.  Per feature
+ * f < f_cols, over the included members (n_a, n_b of them): the means, the unbiased variances by two passes,
+ * s_p = sqrt(((n_a - 1) var_a + (n_b - 1) var_b) / (n_a + n_b - 2)), d = (mean_a - mean_b) / s_p (0 if s_p == 0),
+ * g = d (1 - 3 / (4 (n_a + n_b) - 9)).  With n_a < 2 or n_b < 2 every fp64 output is NaN.
+ * boot int16 [n_boot, n_seg] (nullable: n_boot = 0; else 2 <= n_boot <= WSAE_BOOT_MAX_R): resampling weights, negative
+ * ones count as 0.  Per replicate and group: N = sum w, z = x - mean_g (the observed mean), S1 = sum w z,
+ * S2 = sum w z^2, mean* = mean_g + S1 / N, var* = max(S2 - S1^2 / N, 0) / (N - 1), d* as above; a replicate with either
+ * N < 2 is dropped.  Over the kept replicates (R' of them), sorted: ci_lo / ci_hi are the alpha / 2 and 1 - alpha / 2
+ * quantiles by linear interpolation at position (R' - 1) q, se the sample standard deviation (n - 1, two passes).
+ * Without boot ci_lo, ci_hi and se are NaN.  0 < alpha < 1.
+ * Outputs: fp64 [f_cols] each mean_a, mean_b, d, g, ci_lo, ci_hi, se; record int32 [3] = n_a, n_b, kept replicates.
+ * Every sum over segments runs in one fixed order per (replicate, feature): the result of a column depends on that
+ * column, div, group and boot alone - not on the tile it sits in, its neighbours or ld - and two calls give the same
+ * bits.  1 <= n_seg <= 2^20.  Workspace (16-byte aligned): wsae_group_effect_workspace_bytes - the segment selectors,
+ * the replicate totals and the weights transposed to [segment][replicate]; -1 for invalid arguments. */
+#define WSAE_POOL_MAX_K 128
+#define WSAE_BOOT_MAX_R 2048
+int64_t wsae_pool_workspace_bytes(int64_t n_rows, int32_t k, int32_t hidden, int32_t n_seg, int32_t f_lo, int32_t f_cols);
+int wsae_pool_update(const float* vals, const int32_t* idx, int32_t k, int32_t hidden, const int32_t* seg, int64_t n_rows,
+                     int32_t n_seg, int32_t f_lo, int32_t f_cols, float* pooled_sum, int32_t* pooled_cnt, int64_t ld,
+                     int32_t* seg_rows, void* workspace, int64_t workspace_bytes, void* stream);
+int64_t wsae_group_effect_workspace_bytes(int32_t n_seg, int32_t f_cols, int32_t n_boot);
+int wsae_group_effect(const float* X, int64_t ld, const int32_t* div, const int32_t* group, int32_t n_seg, int32_t f_cols,
+                      const int16_t* boot, int32_t n_boot, double alpha, double* mean_a, double* mean_b, double* d, double* g,
+                      double* ci_lo, double* ci_hi, double* se, int32_t* record, void* workspace, int64_t workspace_bytes,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif
