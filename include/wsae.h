@@ -599,6 +599,41 @@ int wsae_group_effect(const float* X, int64_t ld, const int32_t* div, const int3
                       double* ci_lo, double* ci_hi, double* se, int32_t* record, void* workspace, int64_t workspace_bytes,
                       void* stream);
 
+/* ---- temporal run statistics: run lengths, gaps and event lists -----------------------------------
+ * How long a feature stays on, how long it stays away and where in the utterance it fires, straight from a compact code
+ * vals / idx [n_rows, k] (as wsae_encode_topk writes them, 1 <= k <= WSAE_RUNS_MAX_K) whose rows are in time order.
+ * Ctx-free; the caller's stream, no allocation, no host synchronisation, no float atomics; argument errors are found on
+ * the host before any HIP call.  seg int32 [n_rows] names the segment (utterance) of each row; a row with seg < 0 or
+ * seg >= n_seg is padding.  Feature f is active on row r iff some entry of the row has idx == f, v > 0 and
+ * 0 <= f < hidden (the rule of wsae_coact_update); an index repeated within a row counts once, with the value of its
+ * first active entry.  A run of f in segment s is a maximal set of rows a..b with consecutive row numbers, all of them
+ * of segment s, on all of which f is active: a padding row or a row of another id ends a run, and so does the call
+ * (segments are local to a call; pass whole utterances).  Its length is d = b - a + 1, its start a - (the first row of s
+ * in the call), its total the fp32 sum of its values in ascending row order (sequential float32 adds reproduce it), its
+ * peak their maximum.  Between two consecutive runs of f in the same segment lies a gap g = a_next - b_prev - 1 >= 1, a
+ * difference of row numbers whatever lies between.  Both histograms have WSAE_RUNS_BINS bins: x <= 32 falls into bin
+ * x - 1, a larger x into bin min(32 + floor(log2(x - 1)) - 5, 47), i.e. bin 32 + j holds (2^(5+j), 2^(6+j)].
+ * State (caller-owned, zero-initialised device memory), per feature of the window f_lo <= f < f_lo + f_cols: frames
+ * int32 (sum of d), runs int32, dur_max int32, dur_sq int64 (sum of d^2), dur_hist int32 [f_cols, 48], gap_hist int32
+ * [f_cols, 48] (nullable); total_rows int64 [1] += the non-padding rows.  Every field is an integer sum or maximum
+ * updated with integer atomics: the state does not depend on the launch geometry, on the order of the calls or on how
+ * whole utterances are grouped into calls.
+ * Events (ev_count nullable = none).  Every run with d >= ev_min_len (>= 1) takes a slot from the cursor ev_count int64
+ * [1]; a slot below ev_cap receives ev_int [slot] = (feature, seg_base + s, start, d) and ev_flt [slot] = (total, peak)
+ * (ev_int int32 [ev_cap, 4], ev_flt fp32 [ev_cap, 2]; with ev_cap == 0 both may be NULL and the call only counts).  The
+ * cursor keeps counting past the capacity, so the caller sees how many records were dropped; the statistics do not
+ * depend on the event arguments.  Records arrive in no particular order: sort by (feature, segment, start), which is
+ * unique.  0 <= n_rows <= 2^31 - 1 per call.  Workspace: wsae_runs_workspace_bytes (8 n_seg bytes: the first and last
+ * row of each segment; -1 for invalid arguments), contents arbitrary on entry. */
+#define WSAE_RUNS_MAX_K 128
+#define WSAE_RUNS_BINS 48
+int64_t wsae_runs_workspace_bytes(int64_t n_rows, int32_t k, int32_t hidden, int32_t n_seg, int32_t f_lo, int32_t f_cols);
+int wsae_runs_update(const float* vals, const int32_t* idx, int32_t k, int32_t hidden, const int32_t* seg, int64_t n_rows,
+                     int32_t n_seg, int32_t seg_base, int32_t f_lo, int32_t f_cols, int32_t* frames, int32_t* runs,
+                     int32_t* dur_max, int64_t* dur_sq, int32_t* dur_hist, int32_t* gap_hist, int64_t* total_rows,
+                     int32_t* ev_int, float* ev_flt, int64_t ev_cap, int32_t ev_min_len, int64_t* ev_count, void* workspace,
+                     int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

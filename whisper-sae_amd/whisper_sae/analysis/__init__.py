@@ -1,7 +1,8 @@
 """Feature analysis right after the SAE path: per-feature top activations kept on the
 device, the comparison of two dictionaries by their decoder (or encoder) directions, co-activation statistics of
-their codes, and effect sizes of the features between two groups of utterances.  Mirrors the names of the reference's
-``whisper_sae.analysis.feature_viz`` that sit on that path."""
+their codes, effect sizes of the features between two groups of utterances, and the temporal run statistics of the
+features (run lengths, gaps, event lists).  Mirrors the names of the reference's ``whisper_sae.analysis.feature_viz``
+that sit on that path."""
 
 from .coactivation import (CoactivationNeighbors, CoactivationTracker, collect_coactivation,
                            compare_activations)
@@ -9,8 +10,10 @@ from .dictionary import NearestFeatures, compare_dictionaries, duplicate_feature
 from .feature_viz import FeatureActivation, TopKTracker, collect_top_activations
 from .group_stats import (GroupEffects, SegmentPooler, bootstrap_weights, collect_pooled, group_effect_sizes,
                           top_group_features)
+from .temporal import FeatureEvents, RunSummary, RunTracker, collect_runs, summarize_runs, top_temporal_features
 
 __all__ = ["FeatureActivation", "TopKTracker", "collect_top_activations", "NearestFeatures", "nearest_features",
            "compare_dictionaries", "duplicate_features", "CoactivationNeighbors", "CoactivationTracker",
            "collect_coactivation", "compare_activations", "GroupEffects", "SegmentPooler", "bootstrap_weights",
-           "collect_pooled", "group_effect_sizes", "top_group_features"]
+           "collect_pooled", "group_effect_sizes", "top_group_features", "FeatureEvents", "RunSummary", "RunTracker",
+           "collect_runs", "summarize_runs", "top_temporal_features"]
