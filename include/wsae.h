@@ -267,7 +267,10 @@ int wsae_input_grad(wsae_ctx* ctx, const float* params, const int32_t* idx, cons
  *   if the preceding backward on this ctx left any (wsae_relu_backward does on its row-major-GEMM flow), else recompute.
  * last_activated (nullable) / step_count / dead_threshold: when given, stats->dead_count and
  *   stats->dead_ratio are written (get_dead_feature_ratio() of training.py:212).
- * All four buffers use the flat pack layout. */
+ * All four buffers use the flat pack layout.
+ * lr, beta1, beta2, eps, weight_decay are doubles, as torch holds them: 1 - beta1, 1 - beta2, 1 - lr * weight_decay and the
+ * bias corrections are formed in double and rounded once to fp32, so exp_avg / exp_avg_sq carry torch.optim.AdamW's own
+ * constants (float32(1 - beta), not 1 - float32(beta), which is 1.29e-5 away for beta2 = 0.999). */
 /* Data parallel: turn the SUMMED wire (layout above, P + hidden_dim elements of wire_dtype) into the fp32 buffer
  * `grads_ext` = [gradient pack in pack order | fired] that wsae_adamw_step reads, and leave the gradient part's
  * squared-norm partials in the ctx, so that the following wsae_adamw_step(norm_from_wgrad = 1, grad_scale = 1 / world)
@@ -288,8 +291,8 @@ int wsae_ctx_set_wire_metrics(wsae_ctx* ctx, const float* loss_l0);
 int wsae_grads_unpack_wire(wsae_ctx* ctx, const void* wire, int32_t wire_dtype, float* grads_ext,
                            const float* metrics_sum, int32_t world, wsae_stats* stats, void* stream);
 int wsae_adamw_step(wsae_ctx* ctx, float* params, const float* grads, float* exp_avg,
-                    float* exp_avg_sq, float lr, float beta1, float beta2, float eps,
-                    float weight_decay, int32_t step, float max_norm, float grad_scale,
+                    float* exp_avg_sq, double lr, double beta1, double beta2, double eps,
+                    double weight_decay, int32_t step, float max_norm, float grad_scale,
                     int32_t normalize_decoder, int32_t norm_from_wgrad,
                     int64_t* last_activated, const int64_t* step_count,
                     int64_t dead_threshold, wsae_stats* stats, void* stream);
@@ -310,7 +313,9 @@ int wsae_dead_scan(wsae_ctx* ctx, const int64_t* last_activated, const int64_t* 
  * ascending (at most num_cap, <0 = all), rows by error descending, the L2-normalised raw input row
  * goes to W_e[f,:] and W_dT[f,:], b_e[f] = 0, last_activated[f] = *step_count.  Adam moments
  * untouched.  n_dead_out (device int32): the capped dead count the reference returns
- * (model.py:257), even when fewer than that many rows exist. */
+ * (model.py:257), even when fewer than that many rows exist.  Br <= min(max_batch, 16384): the row sort holds one 64-bit
+ * key per row, rounded up to a power of two, in LDS (128 KB at 16384 rows; wsae_ctx_create raises the kernel's
+ * dynamic-LDS limit for it, and a device that grants a block less than 128 KB is held to 8192 rows). */
 /* Transcoders (sae/transcoder.py:207-252): wsae_row_errors takes the TARGET as x and may also leave the residual
  * rows resid [Br, D] = x - recon (nullable); wsae_resample_dead then writes the L2-normalised row of dec_src
  * (nullable: the residuals) into the decoder column instead of the input direction. */

@@ -117,6 +117,7 @@ struct wsae_ctx {
     int32_t* counters;    // small int scratch (fallback rows, resample cursors; [16..) = arrival tickets, 8-byte aligned)
     int32_t* dead_list;   // [H] compacted dead feature indices (resample)
     int32_t* row_order;   // [maxB] rows sorted by error (resample)
+    int resample_max_rows;  // largest resample batch sort_rows_kernel can launch on this device (wsae_internal_resample_max_rows)
     int relu_fp8;         // 1: the ReLU SAE's two forward GEMMs run on fp8 e4m3 operands (wsae_ctx_set_relu_fp8)
     void* relu_ws;        // ReLU-SAE workspace (wsae_relu.hip), allocated by wsae_ctx_reserve_relu
     int relu_x_B;         // batch size of the last ReLU forward that ran the row-major-GEMM flow (its bf16 hidden is in relu_ws); 0 = none
@@ -271,6 +272,8 @@ __device__ __forceinline__ float load_act(const void* p, int64_t i) {
 
 #endif  // __HIPCC__
 
+// internal (wsae_optim.hip): raise the row sort's dynamic-LDS limit; the largest resample batch that launches (16384 or 8192)
+int wsae_internal_resample_max_rows(int device);
 // internal (wsae_encode.hip): stage the batch (xb, xT) and run the dense encoder GEMM into pre [B][H]
 int wsae_internal_stage(wsae_ctx* ctx, const float* params, const void* x, int x_dtype, const int32_t* rows, int B, hipStream_t st);
 int wsae_internal_stage_rows(wsae_ctx* ctx, const float* params, const void* x, int x_dtype, const int32_t* rows, int B, hipStream_t st);

@@ -89,6 +89,7 @@ extern "C" int wsae_ctx_create(const wsae_config* cfg, wsae_ctx** out) {
         c->cus = 256;
     c->P = wsae_param_count(D, H);
     wsae_param_offsets(D, H, c->off);
+    c->resample_max_rows = wsae_internal_resample_max_rows(cfg->device);
 
     const size_t esz = (c->prec == WSAE_PREC_BF16) ? 2 : 4;
     const size_t maxBp = ((size_t)maxB + 127) / 128 * 128;  // transposed operands are padded to 128 columns

@@ -206,23 +206,31 @@ static int launch_refresh(wsae_ctx* ctx, float* params, bool normalize, const in
 //   clip coefficient from the norm partials -> AdamW on W_e[h,:], W_dT[h,:], b_e[h] -> unit-norm
 //   W_dT[h,:] -> bf16 shadows + folded bias -> dead-feature count.  b_d and b_pre (2D values) are
 //   updated redundantly by every block in registers (the folded bias needs the NEW b_pre) and written
-//   back by block 0 only.  One pass: 28 B/param of traffic, no separate AdamW / renorm / refresh passes.
+//   back by the last block to arrive.  One pass: 28 B/param of traffic, no separate AdamW / renorm / refresh passes.
 // ------------------------------------------------------------------------------------------------
 struct AdamArgs {
-    float max_norm, grad_scale, part_scale, decay, beta1, beta2, eps, step_size, bc2_sqrt, inv_bc2_sqrt;
+    float max_norm, grad_scale, part_scale, decay, beta2, omb1, omb2, eps, step_size, inv_bc2_sqrt;
 };
 
 // torch.optim.AdamW, single step t: p *= 1 - lr*wd; m = lerp(m, g, 1-b1); v = b2 v + (1-b2) g g;
 // denom = sqrt(v)/sqrt(1-b2^t) + eps; p -= (lr/(1-b1^t)) * m/denom.   g is first scaled by gs = clip coefficient *
-// grad_scale (1/world under DDP); decay = 1 - lr*wd, step_size = lr/(1-b1^t), bc2_sqrt = sqrt(1-b2^t) come from the host.
+// grad_scale (1/world under DDP).  Every constant is formed in double on the host from the double hyper-parameters and
+// rounded ONCE to fp32: decay = 1 - lr*wd, omb1 = 1 - b1, omb2 = 1 - b2, step_size = lr/(1-b1^t), inv_bc2_sqrt =
+// 1/sqrt(1-b2^t).  (1.f - float(0.999) is 1.29e-5 away from 0.001; torch multiplies g g by float(0.001).)
+// Every fused multiply-add is written out and implicit contraction is off: update_rows_kernel evaluates this for b_pre in
+// two places (the prologue of every block, for the folded bias, and the last block's write-back), and hipcc contracted the
+// two inlined copies differently - the b_pre behind the fused c_fold was up to 1 ulp away from the b_pre in the pack, so the
+// fused shadows and a later wsae_prepare of the same pack disagreed in the last bit.
 __device__ __forceinline__ float adam1(float p, float g, float& m, float& v, const AdamArgs& a, float gs) {
+#pragma clang fp contract(off)
     const float gc = g * gs;
-    m = m + (gc - m) * (1.f - a.beta1);
-    v = a.beta2 * v + (1.f - a.beta2) * gc * gc;
+    m = fmaf(gc - m, a.omb1, m);
+    v = fmaf(a.beta2, v, a.omb2 * gc * gc);
     // v_sqrt_f32 / v_rcp_f32 (1 ulp each) and a multiplication by 1/sqrt(1-b2^t) instead of the correctly rounded
     // sqrt and two divisions: 40 % fewer vector instructions in the optimizer tail (-1.5 us at cfg 2); the update term is
     // lr-sized, so the parameter moves by < 1e-10 relative against the exact form - inside every pin.
-    return p * a.decay - a.step_size * (m * __builtin_amdgcn_rcpf(__builtin_amdgcn_sqrtf(v) * a.inv_bc2_sqrt + a.eps));
+    const float q = m * __builtin_amdgcn_rcpf(fmaf(__builtin_amdgcn_sqrtf(v), a.inv_bc2_sqrt, a.eps));
+    return fmaf(p, a.decay, -(a.step_size * q));
 }
 
 // Memory-level parallelism: a wave owns ONE feature row and issues every load of it (p, g, m, v of
@@ -427,7 +435,7 @@ extern "C" int wsae_normalize_decoder(wsae_ctx* ctx, float* params, void* stream
 }
 
 extern "C" int wsae_adamw_step(wsae_ctx* ctx, float* params, const float* grads, float* exp_avg, float* exp_avg_sq,
-                               float lr, float beta1, float beta2, float eps, float weight_decay, int32_t step,
+                               double lr, double beta1, double beta2, double eps, double weight_decay, int32_t step,
                                float max_norm, float grad_scale, int32_t normalize_decoder, int32_t norm_from_wgrad,
                                int64_t* last_activated, const int64_t* step_count, int64_t dead_threshold,
                                wsae_stats* stats, void* stream) {
@@ -453,13 +461,13 @@ extern "C" int wsae_adamw_step(wsae_ctx* ctx, float* params, const float* grads,
         WSAE_LAUNCH_CHECK();
     }
     ctx->n_sq_parts = 0;
-    const double bc1 = 1.0 - pow((double)beta1, (double)step);
-    const double bc2 = 1.0 - pow((double)beta2, (double)step);
-    const float step_size = (float)((double)lr / bc1);
-    const float bc2_sqrt = (float)sqrt(bc2);
+    const double bc1 = 1.0 - pow(beta1, (double)step);
+    const double bc2 = 1.0 - pow(beta2, (double)step);
     AdamArgs a;
-    a.max_norm = max_norm; a.grad_scale = grad_scale; a.part_scale = part_scale; a.decay = 1.f - lr * weight_decay;
-    a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.step_size = step_size; a.bc2_sqrt = bc2_sqrt;
+    a.max_norm = max_norm; a.grad_scale = grad_scale; a.part_scale = part_scale;
+    a.decay = (float)(1.0 - lr * weight_decay);
+    a.beta2 = (float)beta2; a.omb1 = (float)(1.0 - beta1); a.omb2 = (float)(1.0 - beta2); a.eps = (float)eps;
+    a.step_size = (float)(lr / bc1);
     a.inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
     const int nb = ceil_div(ctx->H, REFRESH_ROWS);
     const size_t sh = (size_t)ctx->D * sizeof(float);
@@ -604,6 +612,19 @@ __global__ void __launch_bounds__(1024) sort_rows_kernel(const float* __restrict
     for (int i = threadIdx.x; i < Br; i += 1024) order[i] = (int32_t)(~(uint32_t)key[i]);
 }
 
+// The sort keeps one 64-bit key per row (rounded up to a power of two) in dynamic LDS: 64 KB at 8192 rows, 128 KB at 16384.
+// HIP wants a kernel's dynamic-LDS limit raised before a launch above 64 KB; wsae_ctx_create does it once per ctx and keeps
+// the row limit that results (16384 where the device grants a block 128 KB, as the MI355X's 160 KB of LDS per CU does).
+// (ROCm 7 on the MI355X launched the 128 KB sort without the attribute as well; it is set so that this does not rest on that.)
+int wsae_internal_resample_max_rows(int device) {
+    int lds = 0;
+    if (hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerBlock, device) == hipSuccess && lds >= 128 * 1024 &&
+        hipFuncSetAttribute((const void*)sort_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) == hipSuccess)
+        return 16384;
+    (void)hipGetLastError();
+    return 8192;
+}
+
 // rewrite dead feature i with the i-th highest-error input row, L2-normalised (model.py:237-255)
 template <int XDT>
 __global__ void __launch_bounds__(256)
@@ -660,7 +681,7 @@ extern "C" int wsae_resample_dead(wsae_ctx* ctx, float* params, const void* inpu
     const int H = ctx->H, D = ctx->D;
     int npow2 = 1;
     while (npow2 < Br) npow2 <<= 1;
-    WSAE_REQUIRE((size_t)npow2 * 8 <= 128 * 1024, "resample batch %d too large (max 16384 rows)", Br);
+    WSAE_REQUIRE(npow2 <= ctx->resample_max_rows, "resample batch %d too large (max %d rows)", Br, ctx->resample_max_rows);
     WSAE_REQUIRE(Br <= ctx->maxB, "resample batch %d exceeds max_batch %d", Br, ctx->maxB);
     const int cap = num_cap >= 0 ? min(num_cap, H) : H;
     dead_list_kernel<<<1, 1024, 0, st>>>(dead_mask, H, cap, ctx->dead_list, n_dead_out);

@@ -45,7 +45,7 @@ class Stats(C.Structure):
 STATS_WORDS = C.sizeof(Stats) // 4
 
 _p = C.c_void_p
-_i32, _i64, _f32 = C.c_int32, C.c_int64, C.c_float
+_i32, _i64, _f32, _f64 = C.c_int32, C.c_int64, C.c_float, C.c_double
 
 # name -> (restype, argtypes); every symbol include/wsae.h declares
 SIGNATURES = {
@@ -80,7 +80,7 @@ SIGNATURES = {
     "wsae_ctx_set_comm_reserve": (C.c_int, [_p, _i32]),
     "wsae_weight_grads_wire": (C.c_int, [_p, _p, _p, _i32, _p, _p, _p, _p, _i32, _i32, _p, _i32, _p]),
     "wsae_grads_unpack_wire": (C.c_int, [_p, _p, _i32, _p, _p, _i32, _p, _p]),
-    "wsae_adamw_step": (C.c_int, [_p, _p, _p, _p, _p, _f32, _f32, _f32, _f32, _f32, _i32, _f32, _f32, _i32, _i32,
+    "wsae_adamw_step": (C.c_int, [_p, _p, _p, _p, _p, _f64, _f64, _f64, _f64, _f64, _i32, _f32, _f32, _i32, _i32,
                                   _p, _p, _i64, _p, _p]),
     "wsae_normalize_decoder": (C.c_int, [_p, _p, _p]),
     "wsae_dead_scan": (C.c_int, [_p, _p, _p, _i64, _p, _p, _p]),

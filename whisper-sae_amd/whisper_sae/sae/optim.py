@@ -7,6 +7,13 @@ It keeps torch's optimizer surface so that the reference's LR schedulers
 (``LinearLR``/``CosineAnnealingLR``/``SequentialLR``) drive ``param_groups[0]["lr"]`` unchanged and
 ``state_dict()`` has the layout of ``torch.optim.AdamW`` (per-parameter ``step`` / ``exp_avg`` /
 ``exp_avg_sq`` in ``module.parameters()`` order), i.e. checkpoints are interchangeable.
+
+What is guaranteed against ``torch.optim.AdamW``: the hyper-parameters reach the kernel as Python doubles, and ``1 - beta1``,
+``1 - beta2``, ``1 - lr * weight_decay`` and the bias corrections are formed in double and rounded once to float32, which is
+what torch multiplies float32 tensors by.  From zero moments one step leaves ``exp_avg == float32(0.1 g)`` and
+``exp_avg_sq == float32(float32(0.001) g * g)`` to within 2 ulp, and every later step adds only its own fp32 roundings
+(tests/test_gpu_optimizer_tail.py derives and enforces the bound per element; ``denom`` uses the 1-ulp hardware ``sqrt`` and
+``rcp``, which moves a parameter by < 1e-10 relative).
 """
 
 from __future__ import annotations
