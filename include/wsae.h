@@ -639,6 +639,43 @@ int wsae_runs_update(const float* vals, const int32_t* idx, int32_t k, int32_t h
                      int32_t* ev_int, float* ev_flt, int64_t ev_cap, int32_t ev_min_len, int64_t* ev_count, void* workspace,
                      int64_t workspace_bytes, void* stream);
 
+/* ---- feature-triggered averages of a per-frame signal ---------------------------------------------
+ * What is in the input when a feature fires: the average of a dense per-frame signal (log-mel frames, another layer's
+ * residual, a one-hot alignment) around the rows on which a feature is active, straight from a compact code vals / idx
+ * [n_rows, k] (as wsae_encode_topk writes them, 1 <= k <= WSAE_STA_MAX_K) whose rows are in time order.  Ctx-free; the
+ * caller's stream, no allocation, no host synchronisation, no float atomics; argument errors are found on the host
+ * before any HIP call.  seg int32 [n_rows] (nullable = one segment) names the segment (utterance) of each row; a row
+ * with seg < 0 is padding.  y [n_rows, ldy] of y_dtype WSAE_DT_F32 or WSAE_DT_BF16 is the signal: `channels` columns
+ * (1 <= channels <= WSAE_STA_MAX_CH, ldy >= channels), columns from `channels` on are never read.  Lags
+ * -1024 <= lag_lo <= lag_hi <= 1024, L = lag_hi - lag_lo + 1 <= WSAE_STA_MAX_LAGS; 0 need not be among them.
+ * Triggers.  Feature f is active on row r iff the row is not padding and some entry has idx == f, v > 0 and
+ * 0 <= f < hidden (the rule of wsae_runs_update); an index repeated within a row counts once, with the value of its
+ * first active entry.  WSAE_STA_TRIGGER_ALL: every active (row, feature) is a trigger.  WSAE_STA_TRIGGER_ONSET: only
+ * where r == 0, or seg[r - 1] != seg[r], or f is not active on row r - 1.  The weight w of a trigger is v
+ * (WSAE_STA_WEIGHT_VALUE) or 1 (WSAE_STA_WEIGHT_ONE).
+ * Terms.  Trigger (r, f) has a term at lag l iff 0 <= r + l < n_rows and seg[r + l] == seg[r]: lags never cross an
+ * utterance, the signal of a padding row is never read, and a call sees whole utterances.
+ * State (caller-owned, zero-initialised device memory), per feature of the window f_lo <= f < f_lo + f_cols: acc fp64
+ * [f_cols, L, channels], wsum fp64 [f_cols, L], cnt int64 [f_cols, L].  Every term adds double(w) * double(y[r + l][c])
+ * (exact in fp64) to acc[f][l][c], double(w) to wsum[f][l] and 1 to cnt[f][l].  Each cell of acc and wsum is ONE chain
+ * of fp64 additions in ascending trigger row, starting from the stored value: a sequential fp64 loop reproduces the
+ * bits, and they do not depend on the launch geometry, on the tile or window a feature sits in, on ldy, or on how whole
+ * utterances are grouped into calls as long as they arrive in the same order.  0 <= n_rows <= 2^31 - 1 per call.
+ * Workspace (8-byte aligned): wsae_sta_workspace_bytes - the per-feature trigger lists (8 n_rows k bytes), the
+ * [chunks, f_cols] count table and three vectors of f_cols; -1 for invalid arguments; contents arbitrary on entry. */
+#define WSAE_STA_TRIGGER_ALL 0
+#define WSAE_STA_TRIGGER_ONSET 1
+#define WSAE_STA_WEIGHT_VALUE 0
+#define WSAE_STA_WEIGHT_ONE 1
+#define WSAE_STA_MAX_K 128
+#define WSAE_STA_MAX_LAGS 64
+#define WSAE_STA_MAX_CH 4096
+int64_t wsae_sta_workspace_bytes(int64_t n_rows, int32_t k, int32_t hidden, int32_t f_lo, int32_t f_cols);
+int wsae_sta_update(const float* vals, const int32_t* idx, int32_t k, int32_t hidden, const int32_t* seg, int64_t n_rows,
+                    const void* y, int32_t y_dtype, int32_t channels, int64_t ldy, int32_t lag_lo, int32_t lag_hi,
+                    int32_t f_lo, int32_t f_cols, int32_t trigger, int32_t weight, double* acc, double* wsum, int64_t* cnt,
+                    void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

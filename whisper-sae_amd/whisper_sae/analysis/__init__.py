@@ -1,7 +1,7 @@
 """Feature analysis right after the SAE path: per-feature top activations kept on the
 device, the comparison of two dictionaries by their decoder (or encoder) directions, co-activation statistics of
-their codes, effect sizes of the features between two groups of utterances, and the temporal run statistics of the
-features (run lengths, gaps, event lists).  Mirrors the names of the reference's ``whisper_sae.analysis.feature_viz``
+their codes, effect sizes of the features between two groups of utterances, the temporal run statistics of the
+features (run lengths, gaps, event lists), and feature-triggered averages of a per-frame signal.  Mirrors the names of the reference's ``whisper_sae.analysis.feature_viz``
 that sit on that path."""
 
 from .coactivation import (CoactivationNeighbors, CoactivationTracker, collect_coactivation,
@@ -11,9 +11,12 @@ from .feature_viz import FeatureActivation, TopKTracker, collect_top_activations
 from .group_stats import (GroupEffects, SegmentPooler, bootstrap_weights, collect_pooled, group_effect_sizes,
                           top_group_features)
 from .temporal import FeatureEvents, RunSummary, RunTracker, collect_runs, summarize_runs, top_temporal_features
+from .triggered import (TriggeredAverageTracker, as_spectrogram, collect_triggered_averages, mel_frames,
+                        top_template_features)
 
 __all__ = ["FeatureActivation", "TopKTracker", "collect_top_activations", "NearestFeatures", "nearest_features",
            "compare_dictionaries", "duplicate_features", "CoactivationNeighbors", "CoactivationTracker",
            "collect_coactivation", "compare_activations", "GroupEffects", "SegmentPooler", "bootstrap_weights",
            "collect_pooled", "group_effect_sizes", "top_group_features", "FeatureEvents", "RunSummary", "RunTracker",
-           "collect_runs", "summarize_runs", "top_temporal_features"]
+           "collect_runs", "summarize_runs", "top_temporal_features", "TriggeredAverageTracker", "collect_triggered_averages",
+           "mel_frames", "as_spectrogram", "top_template_features"]
