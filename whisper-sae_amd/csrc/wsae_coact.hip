@@ -12,7 +12,7 @@
 #include <limits.h>
 #include <math.h>
 
-#include "wsae_common.h"
+#include "wsae_codewalk.h"
 #include "wsae_toplist.h"
 
 namespace {
@@ -175,8 +175,8 @@ __global__ __launch_bounds__(256) void coact_top_kernel(const int32_t* __restric
 }
 
 bool co_update_args_ok(int64_t n_rows, int k_a, int hidden_a, int k_b, int hidden_b, int64_t a_lo, int64_t a_rows) {
-    return n_rows >= 0 && n_rows <= INT_MAX && k_a >= 1 && k_a <= WSAE_COACT_MAX_K && k_b >= 1 && k_b <= WSAE_COACT_MAX_K &&
-           hidden_a >= 1 && hidden_b >= 1 && a_lo >= 0 && a_rows >= 1 && a_lo + a_rows <= hidden_a;
+    return code_args_ok(n_rows, k_a, WSAE_COACT_MAX_K, hidden_a, a_lo, a_rows) &&
+           code_args_ok(n_rows, k_b, WSAE_COACT_MAX_K, hidden_b, 0, hidden_b);  // (all of B's features)
 }
 
 bool co_top_args_ok(int64_t a_lo, int64_t a_rows, int hidden_b, int top_n) {
@@ -200,10 +200,8 @@ extern "C" int wsae_coact_update(const float* vals_a, const int32_t* idx_a, int3
                  "wsae_coact_update: need 1 <= k_a, k_b <= %d (got %d, %d)", WSAE_COACT_MAX_K, k_a, k_b);
     WSAE_REQUIRE(hidden_a >= 1 && hidden_b >= 1, "wsae_coact_update: hidden_a, hidden_b must be positive (got %d, %d)", hidden_a,
                  hidden_b);
-    WSAE_REQUIRE(n_rows >= 0 && n_rows <= INT_MAX, "wsae_coact_update: need 0 <= n_rows <= 2^31 - 1 (got %lld)",
-                 (long long)n_rows);
-    WSAE_REQUIRE(a_lo >= 0 && a_rows >= 1 && (int64_t)a_lo + a_rows <= hidden_a,
-                 "wsae_coact_update: the window [%d, %d + %d) is outside [0, %d)", a_lo, a_lo, a_rows, hidden_a);
+    CW_REQUIRE_ROWS("wsae_coact_update", n_rows);
+    CW_REQUIRE_WINDOW("wsae_coact_update", a_lo, a_rows, hidden_a);
     WSAE_REQUIRE(ldc >= hidden_b, "wsae_coact_update: ldc %lld < hidden_b %d", (long long)ldc, hidden_b);
     WSAE_REQUIRE(workspace_bytes >= 0, "wsae_coact_update: workspace too small (%lld < 0)", (long long)workspace_bytes);
     if (n_rows == 0) return WSAE_OK;

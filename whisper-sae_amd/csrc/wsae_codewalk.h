@@ -1,0 +1,59 @@
+// What the analysis kernels that walk a compact (values, indices) code share: the LDS pointer
+// types, the per-segment row bounds of a call, and the host-side checks on a code and its feature window.  Included by
+// wsae_groupstats.hip (pooling), wsae_runs.hip, wsae_sta.hip and, for the checks, wsae_coact.hip.
+#pragma once
+#include <limits.h>
+
+#include "wsae_common.h"
+
+namespace {
+
+// LDS is accessed through volatile pointers: the cells are read by other lanes than wrote them, and one wave's LDS
+// instructions execute in order.  (The pointers name the LDS address space themselves: address-space inference leaves
+// volatile accesses alone, and they would be flat.)
+typedef __attribute__((address_space(3))) volatile float lds_f32;
+typedef __attribute__((address_space(3))) volatile int lds_i32;
+typedef __attribute__((address_space(3))) volatile uint8_t lds_u8;
+typedef __attribute__((address_space(3))) volatile unsigned long long lds_u64;
+
+__global__ __launch_bounds__(256) void seg_reset_kernel(int32_t* __restrict__ first, int32_t* __restrict__ last, int n_seg) {
+    const int s = blockIdx.x * 256 + threadIdx.x;
+    if (s < n_seg) {
+        first[s] = INT_MAX;
+        last[s] = -1;
+    }
+}
+
+// first / last row of every segment of this call; a run of equal ids costs two atomics, whatever its length
+__global__ __launch_bounds__(256) void seg_bounds_kernel(const int32_t* __restrict__ seg, int n_rows, int n_seg,
+                                                         int32_t* __restrict__ first, int32_t* __restrict__ last) {
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r >= n_rows) return;
+    const int s = seg[r];
+    if (s < 0 || s >= n_seg) return;
+    if (r == 0 || seg[r - 1] != s) atomicMin(first + s, (int)r);
+    if (r == n_rows - 1 || seg[r + 1] != s) atomicMax(last + s, (int)r);
+}
+
+// first[s] > last[s] afterwards: segment s has no row in this call
+inline void seg_bounds(const int32_t* seg, int64_t n_rows, int n_seg, int32_t* first, int32_t* last, hipStream_t st) {
+    seg_reset_kernel<<<ceil_div(n_seg, 256), 256, 0, st>>>(first, last, n_seg);
+    seg_bounds_kernel<<<(int)ceil_div64(n_rows, 256), 256, 0, st>>>(seg, (int)n_rows, n_seg, first, last);
+}
+
+// ---- host side: the checks every entry point makes on a code and its feature window ------------------------------------
+inline bool code_args_ok(int64_t n_rows, int k, int max_k, int hidden, int64_t f_lo, int64_t f_cols) {
+    return n_rows >= 0 && n_rows <= INT_MAX && k >= 1 && k <= max_k && hidden >= 1 && f_lo >= 0 && f_cols >= 1 &&
+           f_lo + f_cols <= hidden;
+}
+
+// FN: the entry point's name, a string literal.  Three macros, not one: every entry point has checks of its own between
+// them, and the order of the checks decides which message a caller with two mistakes gets.
+#define CW_REQUIRE_K(FN, k, max_k) WSAE_REQUIRE((k) >= 1 && (k) <= (max_k), FN ": need 1 <= k <= %d (got %d)", max_k, k)
+#define CW_REQUIRE_ROWS(FN, n_rows)                                                                                       \
+    WSAE_REQUIRE((n_rows) >= 0 && (n_rows) <= INT_MAX, FN ": need 0 <= n_rows <= 2^31 - 1 (got %lld)", (long long)(n_rows))
+#define CW_REQUIRE_WINDOW(FN, f_lo, f_cols, hidden)                                                                       \
+    WSAE_REQUIRE((f_lo) >= 0 && (f_cols) >= 1 && (int64_t)(f_lo) + (f_cols) <= (hidden),                                  \
+                 FN ": the window [%d, %d + %d) is outside [0, %d)", f_lo, f_lo, f_cols, hidden)
+
+}  // namespace

@@ -2,8 +2,9 @@
 //
 //   pool    segment (utterance) pooling of a compact code: per (segment, feature) the fp32 sum of the active values in
 //           ascending row order, starting from the stored value, plus optional firing counts and the rows per segment.
-//           Three launches: the workspace's per-segment row bounds are reset, found with integer atomics (one per run
-//           of equal segment ids), and then one wave owns a (segment, tile of PL_TILE features) job: the tile's sums sit
+//           Three launches: the per-segment row bounds of the call (seg_bounds of wsae_codewalk.h: reset, then found
+//           with integer atomics, one per run of equal segment ids), and then one wave owns a (segment, tile of
+//           PL_TILE features) job: the tile's sums sit
 //           in LDS, the wave walks the segment's rows in order (four rows of loads in flight), one lane per entry.  A
 //           one-byte LDS tag per column tells whether two entries of one pass name the same column (a TopK code never
 //           does); only then the pass is replayed lane by lane, i.e. in entry order.  One owner per cell and one order:
@@ -21,7 +22,7 @@
 #include <limits.h>
 #include <math.h>
 
-#include "wsae_common.h"
+#include "wsae_codewalk.h"
 
 namespace {
 
@@ -30,32 +31,7 @@ constexpr int PL_TILE = 3072;         // features per job: 12 KB of sums (+ 12 K
 constexpr int PL_MAX_BLOCKS = 2560;   // ten resident single-wave workgroups per CU by LDS; more jobs than that: grid-stride
 constexpr int PL_ROWS = 4;            // rows whose loads are issued before the first of them is accumulated
 
-__global__ __launch_bounds__(256) void pool_reset_kernel(int32_t* __restrict__ first, int32_t* __restrict__ last, int n_seg) {
-    const int s = blockIdx.x * 256 + threadIdx.x;
-    if (s < n_seg) {
-        first[s] = INT_MAX;
-        last[s] = -1;
-    }
-}
-
-// first / last row of every segment of this call; a run of equal ids costs two atomics, whatever its length
-__global__ __launch_bounds__(256) void pool_bounds_kernel(const int32_t* __restrict__ seg, int n_rows, int n_seg,
-                                                          int32_t* __restrict__ first, int32_t* __restrict__ last) {
-    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (r >= n_rows) return;
-    const int s = seg[r];
-    if (s < 0 || s >= n_seg) return;
-    if (r == 0 || seg[r - 1] != s) atomicMin(first + s, (int)r);
-    if (r == n_rows - 1 || seg[r + 1] != s) atomicMax(last + s, (int)r);
-}
-
-// one pass of at most 64 entries (lane = entry) into the wave's tile.  LDS is accessed through volatile pointers: the
-// cells are read by other lanes than wrote them, and one wave's LDS instructions execute in order.  (The pointers name
-// the LDS address space themselves: address-space inference leaves volatile accesses alone, and they would be flat.)
-typedef __attribute__((address_space(3))) volatile float lds_f32;
-typedef __attribute__((address_space(3))) volatile int lds_i32;
-typedef __attribute__((address_space(3))) volatile uint8_t lds_u8;
-
+// one pass of at most 64 entries (lane = entry) into the wave's tile
 template <bool CNT>
 __device__ __forceinline__ void pool_pass(bool in, int c, float v, lds_f32* acc, lds_i32* cn, lds_u8* tag, int lane) {
     if (in) tag[c] = (uint8_t)lane;
@@ -501,11 +477,6 @@ __global__ __launch_bounds__(GE_THREADS) void ge_boot_kernel(const float* __rest
         }
 }
 
-bool pool_args_ok(int64_t n_rows, int k, int hidden, int n_seg, int64_t f_lo, int64_t f_cols) {
-    return n_rows >= 0 && n_rows <= INT_MAX && k >= 1 && k <= WSAE_POOL_MAX_K && hidden >= 1 && n_seg >= 1 && f_lo >= 0 &&
-           f_cols >= 1 && f_lo + f_cols <= hidden;
-}
-
 bool ge_args_ok(int n_seg, int f_cols, int n_boot) {
     return n_seg >= 1 && n_seg <= GE_MAX_SEG && f_cols >= 1 && (n_boot == 0 || (n_boot >= 2 && n_boot <= WSAE_BOOT_MAX_R));
 }
@@ -531,7 +502,8 @@ GeLayout ge_layout(int n_seg, int n_boot) {
 
 extern "C" int64_t wsae_pool_workspace_bytes(int64_t n_rows, int32_t k, int32_t hidden, int32_t n_seg, int32_t f_lo,
                                              int32_t f_cols) {
-    return pool_args_ok(n_rows, k, hidden, n_seg, f_lo, f_cols) ? 8 * (int64_t)n_seg : -1;  // first and last row per segment
+    const bool ok = code_args_ok(n_rows, k, WSAE_POOL_MAX_K, hidden, f_lo, f_cols) && n_seg >= 1;
+    return ok ? 8 * (int64_t)n_seg : -1;  // first and last row per segment
 }
 
 extern "C" int wsae_pool_update(const float* vals, const int32_t* idx, int32_t k, int32_t hidden, const int32_t* seg,
@@ -539,12 +511,10 @@ extern "C" int wsae_pool_update(const float* vals, const int32_t* idx, int32_t k
                                 int32_t* pooled_cnt, int64_t ld, int32_t* seg_rows, void* workspace, int64_t workspace_bytes,
                                 void* stream) {
     WSAE_REQUIRE(vals && idx && seg && pooled_sum && seg_rows, "wsae_pool_update: null pointer");
-    WSAE_REQUIRE(k >= 1 && k <= WSAE_POOL_MAX_K, "wsae_pool_update: need 1 <= k <= %d (got %d)", WSAE_POOL_MAX_K, k);
+    CW_REQUIRE_K("wsae_pool_update", k, WSAE_POOL_MAX_K);
     WSAE_REQUIRE(hidden >= 1 && n_seg >= 1, "wsae_pool_update: hidden and n_seg must be positive (got %d, %d)", hidden, n_seg);
-    WSAE_REQUIRE(n_rows >= 0 && n_rows <= INT_MAX, "wsae_pool_update: need 0 <= n_rows <= 2^31 - 1 (got %lld)",
-                 (long long)n_rows);
-    WSAE_REQUIRE(f_lo >= 0 && f_cols >= 1 && (int64_t)f_lo + f_cols <= hidden,
-                 "wsae_pool_update: the window [%d, %d + %d) is outside [0, %d)", f_lo, f_lo, f_cols, hidden);
+    CW_REQUIRE_ROWS("wsae_pool_update", n_rows);
+    CW_REQUIRE_WINDOW("wsae_pool_update", f_lo, f_cols, hidden);
     WSAE_REQUIRE(ld >= f_cols, "wsae_pool_update: ld %lld < f_cols %d", (long long)ld, f_cols);
     const int64_t need = 8 * (int64_t)n_seg;
     WSAE_REQUIRE(workspace_bytes >= need && (workspace || n_rows == 0), "wsae_pool_update: workspace too small (%lld < %lld)",
@@ -553,8 +523,7 @@ extern "C" int wsae_pool_update(const float* vals, const int32_t* idx, int32_t k
     hipStream_t st = (hipStream_t)stream;
     int32_t* first = (int32_t*)workspace;
     int32_t* last = first + n_seg;
-    pool_reset_kernel<<<ceil_div(n_seg, 256), 256, 0, st>>>(first, last, n_seg);
-    pool_bounds_kernel<<<(int)ceil_div64(n_rows, 256), 256, 0, st>>>(seg, (int)n_rows, n_seg, first, last);
+    seg_bounds(seg, n_rows, n_seg, first, last, st);
     const int n_tiles = ceil_div(f_cols, PL_TILE);
     const int64_t n_jobs = (int64_t)n_seg * n_tiles;
     const int grid = (int)(n_jobs < PL_MAX_BLOCKS ? n_jobs : PL_MAX_BLOCKS);

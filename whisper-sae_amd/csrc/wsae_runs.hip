@@ -3,8 +3,8 @@
 //
 // A run of feature f in segment (utterance) s is a maximal stretch of consecutive rows of the call, all of segment s, on
 // which f is active.  Three launches.  The workspace's per-segment row bounds are reset and found with integer atomics
-// (one pair per stretch of equal ids; the two kernels restate those of wsae_groupstats.hip).  Then a single-wave
-// workgroup owns a (segment, tile of features) job and walks the segment's rows in ascending order (four rows of loads
+// (one pair per stretch of equal ids: seg_bounds of wsae_codewalk.h).  Then a single-wave workgroup
+// owns a (segment, tile of features) job and walks the segment's rows in ascending order (four rows of loads
 // in flight), one lane per entry.  Per tile feature LDS holds the row it was last seen on and the first row of its open
 // run (with events also the run's fp32 sum, in row order, and its peak).  An entry seen on row r continues the run when
 // the feature was seen on r - 1; otherwise it closes the feature's previous run, which also yields the gap, and opens a
@@ -19,7 +19,7 @@
 // active entry.
 #include <limits.h>
 
-#include "wsae_common.h"
+#include "wsae_codewalk.h"
 
 namespace {
 
@@ -29,32 +29,6 @@ constexpr int RN_STAGE = 128;        // event records a wave stages in LDS befor
 constexpr int RN_MAX_BLOCKS = 2560;  // five resident single-wave workgroups per CU by LDS; more jobs than that: grid-stride
 constexpr int RN_ROWS = 4;           // rows whose loads are issued before the first of them is processed
 constexpr int RN_BINS = WSAE_RUNS_BINS;
-
-__global__ __launch_bounds__(256) void runs_reset_kernel(int32_t* __restrict__ first, int32_t* __restrict__ last, int n_seg) {
-    const int s = blockIdx.x * 256 + threadIdx.x;
-    if (s < n_seg) {
-        first[s] = INT_MAX;
-        last[s] = -1;
-    }
-}
-
-// first / last row of every segment of this call; a stretch of equal ids costs two atomics, whatever its length
-__global__ __launch_bounds__(256) void runs_bounds_kernel(const int32_t* __restrict__ seg, int n_rows, int n_seg,
-                                                          int32_t* __restrict__ first, int32_t* __restrict__ last) {
-    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (r >= n_rows) return;
-    const int s = seg[r];
-    if (s < 0 || s >= n_seg) return;
-    if (r == 0 || seg[r - 1] != s) atomicMin(first + s, (int)r);
-    if (r == n_rows - 1 || seg[r + 1] != s) atomicMax(last + s, (int)r);
-}
-
-// LDS is accessed through volatile pointers: the cells are read by other lanes than wrote them, and one wave's LDS
-// instructions execute in order.  (The pointers name the LDS address space themselves: address-space inference leaves
-// volatile accesses alone, and they would be flat.)
-typedef __attribute__((address_space(3))) volatile float lds_f32;
-typedef __attribute__((address_space(3))) volatile int lds_i32;
-typedef __attribute__((address_space(3))) volatile uint8_t lds_u8;
 
 struct RunsOut {
     int32_t* frames;
@@ -287,16 +261,12 @@ __global__ __launch_bounds__(64) void runs_walk_kernel(const float* __restrict__
     if (EV) runs_flush(t, n_staged, o, lane);
 }
 
-bool runs_args_ok(int64_t n_rows, int k, int hidden, int n_seg, int64_t f_lo, int64_t f_cols) {
-    return n_rows >= 0 && n_rows <= INT_MAX && k >= 1 && k <= WSAE_RUNS_MAX_K && hidden >= 1 && n_seg >= 1 && f_lo >= 0 &&
-           f_cols >= 1 && f_lo + f_cols <= hidden;
-}
-
 }  // namespace
 
 extern "C" int64_t wsae_runs_workspace_bytes(int64_t n_rows, int32_t k, int32_t hidden, int32_t n_seg, int32_t f_lo,
                                              int32_t f_cols) {
-    return runs_args_ok(n_rows, k, hidden, n_seg, f_lo, f_cols) ? 8 * (int64_t)n_seg : -1;  // first and last row per segment
+    const bool ok = code_args_ok(n_rows, k, WSAE_RUNS_MAX_K, hidden, f_lo, f_cols) && n_seg >= 1;
+    return ok ? 8 * (int64_t)n_seg : -1;  // first and last row per segment
 }
 
 extern "C" int wsae_runs_update(const float* vals, const int32_t* idx, int32_t k, int32_t hidden, const int32_t* seg,
@@ -306,12 +276,10 @@ extern "C" int wsae_runs_update(const float* vals, const int32_t* idx, int32_t k
                                 int64_t* ev_count, void* workspace, int64_t workspace_bytes, void* stream) {
     WSAE_REQUIRE(vals && idx && seg && frames && runs && dur_max && dur_sq && dur_hist && total_rows,
                  "wsae_runs_update: null pointer");
-    WSAE_REQUIRE(k >= 1 && k <= WSAE_RUNS_MAX_K, "wsae_runs_update: need 1 <= k <= %d (got %d)", WSAE_RUNS_MAX_K, k);
+    CW_REQUIRE_K("wsae_runs_update", k, WSAE_RUNS_MAX_K);
     WSAE_REQUIRE(hidden >= 1 && n_seg >= 1, "wsae_runs_update: hidden and n_seg must be positive (got %d, %d)", hidden, n_seg);
-    WSAE_REQUIRE(n_rows >= 0 && n_rows <= INT_MAX, "wsae_runs_update: need 0 <= n_rows <= 2^31 - 1 (got %lld)",
-                 (long long)n_rows);
-    WSAE_REQUIRE(f_lo >= 0 && f_cols >= 1 && (int64_t)f_lo + f_cols <= hidden,
-                 "wsae_runs_update: the window [%d, %d + %d) is outside [0, %d)", f_lo, f_lo, f_cols, hidden);
+    CW_REQUIRE_ROWS("wsae_runs_update", n_rows);
+    CW_REQUIRE_WINDOW("wsae_runs_update", f_lo, f_cols, hidden);
     WSAE_REQUIRE(seg_base >= 0 && (int64_t)seg_base + n_seg <= INT_MAX,
                  "wsae_runs_update: seg_base %d with %d segments leaves the int32 range", seg_base, n_seg);
     WSAE_REQUIRE(ev_cap >= 0, "wsae_runs_update: ev_cap must not be negative (got %lld)", (long long)ev_cap);
@@ -325,8 +293,7 @@ extern "C" int wsae_runs_update(const float* vals, const int32_t* idx, int32_t k
     hipStream_t st = (hipStream_t)stream;
     int32_t* first = (int32_t*)workspace;
     int32_t* last = first + n_seg;
-    runs_reset_kernel<<<ceil_div(n_seg, 256), 256, 0, st>>>(first, last, n_seg);
-    runs_bounds_kernel<<<(int)ceil_div64(n_rows, 256), 256, 0, st>>>(seg, (int)n_rows, n_seg, first, last);
+    seg_bounds(seg, n_rows, n_seg, first, last, st);
     const bool ev = ev_count != nullptr;  // (with ev_cap == 0 the cursor counts the records a buffer would need)
     RunsOut o;
     o.frames = frames;

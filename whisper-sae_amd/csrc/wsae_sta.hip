@@ -22,7 +22,7 @@
 //      are kept by lane j of the feature's first channel tile.
 #include <limits.h>
 
-#include "wsae_common.h"
+#include "wsae_codewalk.h"
 
 namespace {
 
@@ -34,13 +34,6 @@ constexpr int ST_ROWS = 4;           // rows of the code whose loads are issued 
 constexpr int ST_RB = 8;             // signal rows per block of the accumulation
 constexpr int ST_RING = 128;         // slots of the trigger ring (>= WSAE_STA_MAX_LAGS + ST_RB)
 constexpr int ST_NEVER = INT_MIN + 1000;  // a ring slot that holds no trigger
-
-// LDS is accessed through volatile pointers: the cells are read by other lanes than wrote them, and one wave's LDS
-// instructions execute in order (as wsae_runs.hip).
-typedef __attribute__((address_space(3))) volatile float lds_f32;
-typedef __attribute__((address_space(3))) volatile int lds_i32;
-typedef __attribute__((address_space(3))) volatile uint8_t lds_u8;
-typedef __attribute__((address_space(3))) volatile unsigned long long lds_u64;
 
 struct StaWalk {
     lds_i32* seen;  // the row the feature was last seen on, -2 = not yet
@@ -332,11 +325,6 @@ __global__ __launch_bounds__(64) void sta_accum_kernel(const int32_t* __restrict
     }
 }
 
-bool sta_args_ok(int64_t n_rows, int k, int hidden, int64_t f_lo, int64_t f_cols) {
-    return n_rows >= 0 && n_rows <= INT_MAX && k >= 1 && k <= WSAE_STA_MAX_K && hidden >= 1 && f_lo >= 0 && f_cols >= 1 &&
-           f_lo + f_cols <= hidden;
-}
-
 int64_t sta_align(int64_t b) { return (b + 255) & ~(int64_t)255; }
 
 struct StaPlan {
@@ -365,7 +353,7 @@ StaPlan sta_plan(int64_t n_rows, int k, int f_cols) {
 }  // namespace
 
 extern "C" int64_t wsae_sta_workspace_bytes(int64_t n_rows, int32_t k, int32_t hidden, int32_t f_lo, int32_t f_cols) {
-    return sta_args_ok(n_rows, k, hidden, f_lo, f_cols) ? sta_plan(n_rows, k, f_cols).bytes : -1;
+    return code_args_ok(n_rows, k, WSAE_STA_MAX_K, hidden, f_lo, f_cols) ? sta_plan(n_rows, k, f_cols).bytes : -1;
 }
 
 extern "C" int wsae_sta_update(const float* vals, const int32_t* idx, int32_t k, int32_t hidden, const int32_t* seg,
@@ -373,10 +361,9 @@ extern "C" int wsae_sta_update(const float* vals, const int32_t* idx, int32_t k,
                                int32_t lag_hi, int32_t f_lo, int32_t f_cols, int32_t trigger, int32_t weight, double* acc,
                                double* wsum, int64_t* cnt, void* workspace, int64_t workspace_bytes, void* stream) {
     WSAE_REQUIRE(vals && idx && y && acc && wsum && cnt, "wsae_sta_update: null pointer");
-    WSAE_REQUIRE(k >= 1 && k <= WSAE_STA_MAX_K, "wsae_sta_update: need 1 <= k <= %d (got %d)", WSAE_STA_MAX_K, k);
+    CW_REQUIRE_K("wsae_sta_update", k, WSAE_STA_MAX_K);
     WSAE_REQUIRE(hidden >= 1, "wsae_sta_update: hidden must be positive (got %d)", hidden);
-    WSAE_REQUIRE(n_rows >= 0 && n_rows <= INT_MAX, "wsae_sta_update: need 0 <= n_rows <= 2^31 - 1 (got %lld)",
-                 (long long)n_rows);
+    CW_REQUIRE_ROWS("wsae_sta_update", n_rows);
     WSAE_REQUIRE(y_dtype == WSAE_DT_F32 || y_dtype == WSAE_DT_BF16, "wsae_sta_update: y_dtype must be WSAE_DT_F32 or WSAE_DT_BF16 (got %d)",
                  y_dtype);
     WSAE_REQUIRE(channels >= 1 && channels <= WSAE_STA_MAX_CH, "wsae_sta_update: need 1 <= channels <= %d (got %d)",
@@ -385,8 +372,7 @@ extern "C" int wsae_sta_update(const float* vals, const int32_t* idx, int32_t k,
     WSAE_REQUIRE(lag_lo <= lag_hi && lag_lo >= -1024 && lag_hi <= 1024 && lag_hi - lag_lo + 1 <= WSAE_STA_MAX_LAGS,
                  "wsae_sta_update: need -1024 <= lag_lo <= lag_hi <= 1024 and at most %d lags (got %d .. %d)", WSAE_STA_MAX_LAGS,
                  lag_lo, lag_hi);
-    WSAE_REQUIRE(f_lo >= 0 && f_cols >= 1 && (int64_t)f_lo + f_cols <= hidden,
-                 "wsae_sta_update: the window [%d, %d + %d) is outside [0, %d)", f_lo, f_lo, f_cols, hidden);
+    CW_REQUIRE_WINDOW("wsae_sta_update", f_lo, f_cols, hidden);
     WSAE_REQUIRE(trigger == WSAE_STA_TRIGGER_ALL || trigger == WSAE_STA_TRIGGER_ONSET,
                  "wsae_sta_update: trigger must be WSAE_STA_TRIGGER_ALL or WSAE_STA_TRIGGER_ONSET (got %d)", trigger);
     WSAE_REQUIRE(weight == WSAE_STA_WEIGHT_VALUE || weight == WSAE_STA_WEIGHT_ONE,

@@ -22,6 +22,7 @@ from torch import Tensor
 
 from .. import _native as N
 from ..sae.engine import require_device_tensor
+from . import _stream
 
 _METRICS = {"count": N.COACT_COUNT, "cond": N.COACT_COND, "jaccard": N.COACT_JACCARD, "phi": N.COACT_PHI}
 MAX_ROWS = 2 ** 31 - 1  # the marginals and the table cells are int32
@@ -39,18 +40,7 @@ class CoactivationNeighbors(NamedTuple):
 
 def _code(code, what: str) -> Tuple[Tensor, Tensor]:
     """``(values, indices)`` of any leading shape -> contiguous ``[rows, k]`` float32 / int32 device tensors."""
-    if not (isinstance(code, (tuple, list)) and len(code) == 2):
-        raise TypeError(f"{what} must be a (values, indices) pair")
-    vals, idx = code
-    require_device_tensor(vals, f"{what} values")
-    require_device_tensor(idx, f"{what} indices")
-    if vals.shape != idx.shape or vals.dim() < 1:
-        raise ValueError(f"{what}: values {tuple(vals.shape)} and indices {tuple(idx.shape)} differ in shape")
-    k = vals.shape[-1]
-    if not 1 <= k <= N.COACT_MAX_K:
-        raise ValueError(f"{what}: k must be in 1..{N.COACT_MAX_K}, got {k}")
-    return (vals.detach().reshape(-1, k).to(torch.float32).contiguous(),
-            idx.detach().reshape(-1, k).to(torch.int32).contiguous())
+    return _stream.flat_code(*_stream.compact_code(code, what, N.COACT_MAX_K, dims=None))
 
 
 class CoactivationTracker:
@@ -68,9 +58,7 @@ class CoactivationTracker:
         self.hidden_b = self.hidden_a if hidden_b is None else int(hidden_b)
         if self.hidden_a < 1 or self.hidden_b < 1:
             raise ValueError(f"hidden sizes must be positive, got {hidden_a}, {hidden_b}")
-        self.a_lo, self.a_rows = (0, self.hidden_a) if a_window is None else (int(a_window[0]), int(a_window[1]))
-        if self.a_lo < 0 or self.a_rows < 1 or self.a_lo + self.a_rows > self.hidden_a:
-            raise ValueError(f"a_window {a_window} is outside [0, {self.hidden_a})")
+        self.a_lo, self.a_rows = _stream.feature_window(a_window, self.hidden_a, "a_window")
         self.device = torch.device(device) if device is not None else None
         self._ldc = (self.hidden_b + 3) // 4 * 4  # 16-byte rows: wsae_coact_top then loads 16 bytes per lane
         self._counts: Optional[Tensor] = None
@@ -87,15 +75,7 @@ class CoactivationTracker:
     def _ensure_device(self, like: Optional[Tensor] = None) -> torch.device:
         if self._counts is not None:
             return self._counts.device
-        dev = self.device or (like.device if like is not None else None)
-        if dev is None:
-            if not torch.cuda.is_available():
-                raise N.WsaeError("CoactivationTracker needs a GPU: the tables live in device memory and there is no CPU "
-                                  "implementation")
-            dev = torch.device("cuda", torch.cuda.current_device())
-        if dev.type != "cuda":
-            raise N.WsaeError(f"CoactivationTracker cannot live on '{dev}': its kernels run on the GPU only")
-        N.lib()  # fail loudly when the HIP library is not built
+        dev = _stream.need_gpu("CoactivationTracker", self.device or (like.device if like is not None else None))
         self._counts = torch.zeros(self.a_rows, self._ldc, dtype=torch.int32, device=dev)
         self._fire_a = torch.zeros(self.hidden_a, dtype=torch.int32, device=dev)
         self._fire_b = None if self.is_self else torch.zeros(self.hidden_b, dtype=torch.int32, device=dev)
@@ -254,31 +234,21 @@ def collect_coactivation(model_a, model_b=None, dataloader=None, *, a_window: Op
     if dataloader is None:
         raise TypeError("collect_coactivation needs a dataloader")
     models = [model_a] if model_b is None else [model_a, model_b]
-    for m in models:
-        if not hasattr(m, "encode_compact"):
-            raise TypeError(f"{type(m).__name__} has no compact code (encode_compact): co-activation statistics are for "
-                            f"TopK-family codes; use a dense matrix product for a ReLU SAE")
-    tracker = CoactivationTracker(model_a.hidden_dim, None if model_b is None else model_b.hidden_dim, a_window=a_window,
-                                  device=device)
-    modes = [m.training for m in models]
-    for m in models:
-        m.eval()
-    try:
-        with torch.no_grad():
-            for batch in dataloader:
-                if isinstance(batch, (tuple, list)):
-                    xs = [batch[0], batch[1] if model_b is not None and len(batch) > 1 and isinstance(batch[1], Tensor)
-                          else batch[0]]
-                else:
-                    xs = [batch, batch]
-                if xs[0].shape[:-1] != xs[1].shape[:-1]:
-                    raise ValueError(f"the two inputs of a batch differ in leading shape: {tuple(xs[0].shape)} and "
-                                     f"{tuple(xs[1].shape)}")
-                codes = [m.encode_compact(x.to(device)) for m, x in zip(models, xs)]
-                tracker.update(codes[0], codes[1] if model_b is not None else None)
-    finally:
-        for m, mode in zip(models, modes):
-            m.train(mode)
+    with _stream.encoding(*models, hint="co-activation statistics are for TopK-family codes; use a dense matrix product for a "
+                                  "ReLU SAE"):
+        tracker = CoactivationTracker(model_a.hidden_dim, None if model_b is None else model_b.hidden_dim,
+                                      a_window=a_window, device=device)
+        for batch in dataloader:
+            if isinstance(batch, (tuple, list)):
+                xs = [batch[0], batch[1] if model_b is not None and len(batch) > 1 and isinstance(batch[1], Tensor)
+                      else batch[0]]
+            else:
+                xs = [batch, batch]
+            if xs[0].shape[:-1] != xs[1].shape[:-1]:
+                raise ValueError(f"the two inputs of a batch differ in leading shape: {tuple(xs[0].shape)} and "
+                                 f"{tuple(xs[1].shape)}")
+            codes = [m.encode_compact(x.to(device)) for m, x in zip(models, xs)]
+            tracker.update(codes[0], codes[1] if model_b is not None else None)
     return tracker
 
 

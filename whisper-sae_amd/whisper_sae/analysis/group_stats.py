@@ -22,6 +22,7 @@ from torch import Tensor
 
 from .. import _native as N
 from ..sae.engine import require_device_tensor
+from . import _stream
 
 MAX_FRAMES = 2 ** 31 - 1  # seg_rows and the counts are int32
 
@@ -43,17 +44,6 @@ class GroupEffects(NamedTuple):
     n_boot: int
 
 
-def _need_gpu(what: str, dev: Optional[torch.device]) -> torch.device:
-    if dev is None:
-        if not torch.cuda.is_available():
-            raise N.WsaeError(f"{what} needs a GPU: its kernels run on the device and there is no CPU implementation")
-        dev = torch.device("cuda", torch.cuda.current_device())
-    if dev.type != "cuda":
-        raise N.WsaeError(f"{what} cannot run on '{dev}': its kernels run on the GPU only")
-    N.lib()  # fail loudly when the HIP library is not built
-    return dev
-
-
 class SegmentPooler:
     """Per-utterance sums of a compact code.
 
@@ -66,9 +56,7 @@ class SegmentPooler:
         self.hidden, self.n_segments = int(hidden), int(n_segments)
         if self.hidden < 1 or self.n_segments < 1:
             raise ValueError(f"hidden and n_segments must be positive, got {hidden}, {n_segments}")
-        self.f_lo, self.f_cols = (0, self.hidden) if f_window is None else (int(f_window[0]), int(f_window[1]))
-        if self.f_lo < 0 or self.f_cols < 1 or self.f_lo + self.f_cols > self.hidden:
-            raise ValueError(f"f_window {f_window} is outside [0, {self.hidden})")
+        self.f_lo, self.f_cols = _stream.feature_window(f_window, self.hidden)
         self.with_counts = bool(counts)
         self.device = torch.device(device) if device is not None else None
         self._ld = (self.f_cols + 3) // 4 * 4
@@ -83,7 +71,7 @@ class SegmentPooler:
     def _ensure_device(self, like: Optional[Tensor] = None) -> torch.device:
         if self._sum is not None:
             return self._sum.device
-        dev = _need_gpu("SegmentPooler", self.device or (like.device if like is not None else None))
+        dev = _stream.need_gpu("SegmentPooler", self.device or (like.device if like is not None else None))
         self._sum = torch.zeros(self.n_segments, self._ld, dtype=torch.float32, device=dev)
         self._cnt = torch.zeros(self.n_segments, self._ld, dtype=torch.int32, device=dev) if self.with_counts else None
         self._rows = torch.zeros(self.n_segments, dtype=torch.int32, device=dev)
@@ -124,52 +112,21 @@ class SegmentPooler:
         base (``segments`` must be None), or flat ``[rows, k]`` with ``segments [rows]`` (ids outside
         ``0 .. n_segments - 1`` mark padding; the frames of an utterance should arrive together).  Frames with
         ``frame_mask == 0`` contribute nothing."""
-        if not (isinstance(code, (tuple, list)) and len(code) == 2):
-            raise TypeError("code must be a (values, indices) pair")
-        vals, idx = code
-        require_device_tensor(vals, "code values")
-        require_device_tensor(idx, "code indices")
-        if vals.shape != idx.shape or vals.dim() not in (2, 3):
-            raise ValueError(f"code: values {tuple(vals.shape)} and indices {tuple(idx.shape)} must share a [n_utt, T, k] or "
-                             f"[rows, k] shape")
-        k = vals.shape[-1]
-        if not 1 <= k <= N.POOL_MAX_K:
-            raise ValueError(f"code: k must be in 1..{N.POOL_MAX_K}, got {k}")
+        vals, idx, k = _stream.compact_code(code, "code", N.POOL_MAX_K)
         dev = self._ensure_device(vals)
         if vals.device != dev:
             raise N.WsaeError(f"the code is on {vals.device}, the pooler on {dev}")
-        used = 0
-        if vals.dim() == 3:
-            if segments is not None:
-                raise ValueError("a [n_utt, T, k] code numbers its utterances itself: pass segments only with a flat code")
-            n_utt, T = vals.shape[0], vals.shape[1]
-            if self._next + n_utt > self.n_segments:
-                raise ValueError(f"{self._next} + {n_utt} utterances exceed n_segments = {self.n_segments}")
-            seg = (torch.arange(self._next, self._next + n_utt, dtype=torch.int32, device=dev)[:, None]
-                   .expand(n_utt, T).reshape(-1))
-            used = n_utt
-        else:
-            if segments is None:
-                raise ValueError("a flat [rows, k] code needs segments [rows]")
-            require_device_tensor(segments, "segments")
-            if segments.numel() != vals.shape[0]:
-                raise ValueError(f"segments has {segments.numel()} ids for {vals.shape[0]} rows")
-            seg = segments.detach().reshape(-1).to(device=dev, dtype=torch.int32)
-        rows = seg.shape[0]
-        if frame_mask is not None:
-            require_device_tensor(frame_mask, "frame_mask")
-            if frame_mask.numel() != rows:
-                raise ValueError(f"frame_mask has {frame_mask.numel()} flags for {rows} frames")
-            seg = torch.where(frame_mask.detach().reshape(-1).to(dev) != 0, seg, torch.full_like(seg, -1))
+        seg, n_utt = _stream.frame_segments(vals, segments, frame_mask, dev, first=self._next)
+        used, rows = n_utt or 0, seg.shape[0]
+        if self._next + used > self.n_segments:
+            raise ValueError(f"{self._next} + {used} utterances exceed n_segments = {self.n_segments}")
         if self._submitted + rows > MAX_FRAMES:
             raise N.WsaeError(f"SegmentPooler: {self._submitted} + {rows} frames exceed {MAX_FRAMES}, the range of the int32 "
                               f"state")
         if rows == 0:
             self._next += used
             return
-        v = vals.detach().reshape(-1, k).to(torch.float32).contiguous()
-        i = idx.detach().reshape(-1, k).to(torch.int32).contiguous()
-        seg = seg.contiguous()
+        v, i = _stream.flat_code(vals, idx, k)
         with torch.cuda.device(dev):
             N.check(N.lib().wsae_pool_update(
                 v.data_ptr(), i.data_ptr(), k, self.hidden, seg.data_ptr(), rows, self.n_segments, self.f_lo, self.f_cols,
@@ -279,7 +236,7 @@ def group_effect_sizes(pooled_or_matrix, labels, *, group_a=0, group_b=1, n_boot
         if X.dim() != 2 or X.dtype != torch.float32:
             raise ValueError(f"the per-utterance matrix must be [S, H] float32, got {tuple(X.shape)} {X.dtype}")
         X = X.detach().contiguous()
-        dev = _need_gpu("group_effect_sizes", X.device)
+        dev = _stream.need_gpu("group_effect_sizes", X.device)
         S, f_cols = X.shape
         ld = f_cols
     else:
@@ -304,9 +261,7 @@ def top_group_features(effects: GroupEffects, n: int = 20, require_ci_excludes_z
     ok = torch.isfinite(score)
     if require_ci_excludes_zero:
         ok &= (effects.ci_lo > 0) | (effects.ci_hi < 0)
-    score = torch.where(ok, score, torch.full_like(score, -1.0))
-    order = torch.argsort(score, descending=True, stable=True)[:int(n)]
-    order = order[score[order] >= 0]
+    order = _stream.rank_features(score, ok, n)
     return order, effects.g[order]
 
 
@@ -317,24 +272,14 @@ def collect_pooled(model, utterances, *, n_segments: Optional[int] = None, f_win
     of a list.  The module must offer ``encode_compact`` (TopK and BatchTopK SAEs; for a ReLU SAE pool the dense code in
     torch and pass the matrix to ``group_effect_sizes``: ``TypeError``) and is run in eval mode; its previous mode is
     restored."""
-    if not hasattr(model, "encode_compact"):
-        raise TypeError(f"{type(model).__name__} has no compact code (encode_compact): pool its dense code in torch and pass "
-                        f"the [S, H] matrix to group_effect_sizes")
-    if n_segments is None:
-        utterances = list(utterances)
-        n_segments = sum((b[0] if isinstance(b, (tuple, list)) else b).shape[0] for b in utterances)
-    pooler = SegmentPooler(model.hidden_dim, n_segments, f_window=f_window, counts=counts, device=device)
-    mode = model.training
-    model.eval()
-    try:
-        with torch.no_grad():
-            for batch in utterances:
-                x, mask = (batch[0], batch[1]) if isinstance(batch, (tuple, list)) else (batch, None)
-                if x.dim() != 3:
-                    raise ValueError(f"an utterance batch must be [n_utt, T, D], got {tuple(x.shape)}")
-                vals, idx = model.encode_compact(x.to(device))
-                shape = (x.shape[0], x.shape[1], vals.shape[-1])
-                pooler.update((vals.reshape(shape), idx.reshape(shape)), frame_mask=None if mask is None else mask.to(device))
-    finally:
-        model.train(mode)
+    with _stream.encoding(model, hint="pool its dense code in torch and pass the [S, H] matrix to group_effect_sizes"):
+        if n_segments is None:
+            utterances = list(utterances)
+            n_segments = sum((b[0] if isinstance(b, (tuple, list)) else b).shape[0] for b in utterances)
+        pooler = SegmentPooler(model.hidden_dim, n_segments, f_window=f_window, counts=counts, device=device)
+        for batch in utterances:
+            x, mask = (batch[0], batch[1]) if isinstance(batch, (tuple, list)) else (batch, None)
+            if x.dim() != 3:
+                raise ValueError(f"an utterance batch must be [n_utt, T, D], got {tuple(x.shape)}")
+            pooler.update(_stream.utterance_code(model, x, device), frame_mask=None if mask is None else mask.to(device))
     return pooler

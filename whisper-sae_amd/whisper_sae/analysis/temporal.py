@@ -24,8 +24,7 @@ import torch
 from torch import Tensor
 
 from .. import _native as N
-from ..sae.engine import require_device_tensor
-from .group_stats import _need_gpu
+from . import _stream
 
 MAX_ROWS = 2 ** 31 - 1  # frames, runs and the histogram cells are int32
 RUNS_BINS = N.RUNS_BINS
@@ -126,9 +125,7 @@ class RunTracker:
         self.hidden = int(hidden)
         if self.hidden < 1:
             raise ValueError(f"hidden must be positive, got {hidden}")
-        self.f_lo, self.f_cols = (0, self.hidden) if f_window is None else (int(f_window[0]), int(f_window[1]))
-        if self.f_lo < 0 or self.f_cols < 1 or self.f_lo + self.f_cols > self.hidden:
-            raise ValueError(f"f_window {f_window} is outside [0, {self.hidden})")
+        self.f_lo, self.f_cols = _stream.feature_window(f_window, self.hidden)
         self.with_gaps = bool(gaps)
         self.max_events, self.min_event_len = int(max_events), int(min_event_len)
         if self.max_events < 0 or self.min_event_len < 1:
@@ -144,7 +141,7 @@ class RunTracker:
     def _ensure_device(self, like: Optional[Tensor] = None) -> torch.device:
         if self._state is not None:
             return self._state["frames"].device
-        dev = _need_gpu("RunTracker", self.device or (like.device if like is not None else None))
+        dev = _stream.need_gpu("RunTracker", self.device or (like.device if like is not None else None))
         z = lambda *shape, dtype=torch.int32: torch.zeros(*shape, dtype=dtype, device=dev)  # noqa: E731
         st = {"frames": z(self.f_cols), "runs": z(self.f_cols), "dur_max": z(self.f_cols),
               "dur_sq": z(self.f_cols, dtype=torch.int64), "dur_hist": z(self.f_cols, RUNS_BINS),
@@ -188,49 +185,18 @@ class RunTracker:
         from the device), its workspace and job count grow with the span of the numbers of one call, and the events carry
         the caller's numbers.  A tracker takes one of the two forms, not both.  Frames with ``frame_mask == 0`` are
         padding: they end a run and count for nothing."""
-        if not (isinstance(code, (tuple, list)) and len(code) == 2):
-            raise TypeError("code must be a (values, indices) pair")
-        vals, idx = code
-        require_device_tensor(vals, "code values")
-        require_device_tensor(idx, "code indices")
-        if vals.shape != idx.shape or vals.dim() not in (2, 3):
-            raise ValueError(f"code: values {tuple(vals.shape)} and indices {tuple(idx.shape)} must share a [n_utt, T, k] or "
-                             f"[rows, k] shape")
-        k = vals.shape[-1]
-        if not 1 <= k <= N.RUNS_MAX_K:
-            raise ValueError(f"code: k must be in 1..{N.RUNS_MAX_K}, got {k}")
+        vals, idx, k = _stream.compact_code(code, "code", N.RUNS_MAX_K)
         dev = self._ensure_device(vals)
         if vals.device != dev:
             raise N.WsaeError(f"the code is on {vals.device}, the tracker on {dev}")
-        form = "numbered" if vals.dim() == 3 else "flat"
-        if self._form not in (None, form):
-            raise ValueError(f"this tracker has taken {self._form} updates: [n_utt, T, k] codes and flat codes with segments "
-                             f"number their utterances differently and cannot be mixed")
-        used, base = 0, 0
-        if vals.dim() == 3:
-            if segments is not None:
-                raise ValueError("a [n_utt, T, k] code numbers its utterances itself: pass segments only with a flat code")
-            n_utt, T = vals.shape[0], vals.shape[1]
-            seg = torch.arange(n_utt, dtype=torch.int32, device=dev)[:, None].expand(n_utt, T).reshape(-1)
-            used, base, n_seg = n_utt, self._next, n_utt
-        else:
-            if segments is None:
-                raise ValueError("a flat [rows, k] code needs segments [rows]")
-            require_device_tensor(segments, "segments")
-            if segments.numel() != vals.shape[0]:
-                raise ValueError(f"segments has {segments.numel()} ids for {vals.shape[0]} rows")
-            seg = segments.detach().reshape(-1).to(device=dev, dtype=torch.int32)
-            n_seg = -1  # (read back below, once the frame mask is applied)
-        rows = seg.shape[0]
-        if frame_mask is not None:
-            require_device_tensor(frame_mask, "frame_mask")
-            if frame_mask.numel() != rows:
-                raise ValueError(f"frame_mask has {frame_mask.numel()} flags for {rows} frames")
-            seg = torch.where(frame_mask.detach().reshape(-1).to(dev) != 0, seg, torch.full_like(seg, -1))
+        form = _stream.take_form(self, vals, "number their utterances differently and ")
+        seg, n_utt = _stream.frame_segments(vals, segments, frame_mask, dev)
+        used, rows = n_utt or 0, seg.shape[0]
+        base, n_seg = self._next, used  # (a flat code: read back below)
         if self._submitted + rows > MAX_ROWS:
             raise N.WsaeError(f"RunTracker: {self._submitted} + {rows} frames exceed {MAX_ROWS}, the range of the int32 state")
-        if rows and n_seg < 0:
-            live = seg >= 0
+        if rows and n_utt is None:
+            base, live = 0, seg >= 0
             hi = int(seg.max().item())
             if hi >= 0:  # (else padding only: n_seg stays below 1)
                 base = int(torch.where(live, seg, torch.full_like(seg, hi)).min().item())
@@ -241,13 +207,10 @@ class RunTracker:
             self._submitted += rows
             self._form = form
             return
-        v = vals.detach().reshape(-1, k).to(torch.float32).contiguous()
-        i = idx.detach().reshape(-1, k).to(torch.int32).contiguous()
-        seg = seg.contiguous()
+        v, i = _stream.flat_code(vals, idx, k)
         st = self._state
         with torch.cuda.device(dev):
-            if self._ws is None or self._ws.numel() < 2 * n_seg:
-                self._ws = torch.empty(2 * n_seg, dtype=torch.int32, device=dev)
+            _stream.grow(self, 2 * n_seg, torch.int32, dev)
             N.check(N.lib().wsae_runs_update(
                 v.data_ptr(), i.data_ptr(), k, self.hidden, seg.data_ptr(), rows, n_seg, base, self.f_lo, self.f_cols,
                 st["frames"].data_ptr(), st["runs"].data_ptr(), st["dur_max"].data_ptr(), st["dur_sq"].data_ptr(),
@@ -366,10 +329,7 @@ def top_temporal_features(summary: RunSummary, by: str = "mean_duration", n: int
         raise ValueError(f"by must be one of {RunSummary._fields}, got {by!r}")
     value = getattr(summary, by).double()
     ok = (summary.runs >= int(min_runs)) & ~torch.isnan(value)
-    score = value if largest else -value
-    score = torch.where(ok, score, torch.full_like(score, float("-inf")))
-    order = torch.argsort(score, descending=True, stable=True)[:max(int(n), 0)]
-    order = order[ok[order]]
+    order = _stream.rank_features(value if largest else -value, ok, n)
     return order, getattr(summary, by)[order]
 
 
@@ -378,21 +338,11 @@ def collect_runs(model, utterances, *, device="cuda", **tracker_kw) -> RunTracke
     ``(x, frame_mask [n_utt, T])``; utterances are numbered in the order they arrive.  ``tracker_kw`` goes to
     ``RunTracker``.  The module must offer ``encode_compact`` (TopK and BatchTopK SAEs; a ReLU SAE's code is dense:
     ``TypeError``) and is run in eval mode; its previous mode is restored."""
-    if not hasattr(model, "encode_compact"):
-        raise TypeError(f"{type(model).__name__} has no compact code (encode_compact): run statistics are for TopK-family "
-                        f"codes")
-    tracker = RunTracker(model.hidden_dim, device=device, **tracker_kw)
-    mode = model.training
-    model.eval()
-    try:
-        with torch.no_grad():
-            for batch in utterances:
-                x, mask = (batch[0], batch[1]) if isinstance(batch, (tuple, list)) else (batch, None)
-                if x.dim() != 3:
-                    raise ValueError(f"an utterance batch must be [n_utt, T, D], got {tuple(x.shape)}")
-                vals, idx = model.encode_compact(x.to(device))
-                shape = (x.shape[0], x.shape[1], vals.shape[-1])
-                tracker.update((vals.reshape(shape), idx.reshape(shape)), frame_mask=None if mask is None else mask.to(device))
-    finally:
-        model.train(mode)
+    with _stream.encoding(model, hint="run statistics are for TopK-family codes"):
+        tracker = RunTracker(model.hidden_dim, device=device, **tracker_kw)
+        for batch in utterances:
+            x, mask = (batch[0], batch[1]) if isinstance(batch, (tuple, list)) else (batch, None)
+            if x.dim() != 3:
+                raise ValueError(f"an utterance batch must be [n_utt, T, D], got {tuple(x.shape)}")
+            tracker.update(_stream.utterance_code(model, x, device), frame_mask=None if mask is None else mask.to(device))
     return tracker

@@ -22,8 +22,7 @@ import torch
 from torch import Tensor
 
 from .. import _native as N
-from ..sae.engine import require_device_tensor
-from .group_stats import _need_gpu
+from . import _stream
 
 MAX_ROWS = 2 ** 31 - 1
 TRIGGERS = {"all": N.STA_TRIGGER_ALL, "onset": N.STA_TRIGGER_ONSET}
@@ -96,9 +95,7 @@ class TriggeredAverageTracker:
             raise ValueError(f"trigger must be one of {tuple(TRIGGERS)} and weight one of {tuple(WEIGHTS)}, got {trigger!r}, "
                              f"{weight!r}")
         self.trigger, self.weight = trigger, weight
-        self.f_lo, self.f_cols = (0, self.hidden) if f_window is None else (int(f_window[0]), int(f_window[1]))
-        if self.f_lo < 0 or self.f_cols < 1 or self.f_lo + self.f_cols > self.hidden:
-            raise ValueError(f"f_window {f_window} is outside [0, {self.hidden})")
+        self.f_lo, self.f_cols = _stream.feature_window(f_window, self.hidden)
         self.device = torch.device(device) if device is not None else None
         self._state: Optional[dict] = None
         self._ws: Optional[Tensor] = None
@@ -110,7 +107,7 @@ class TriggeredAverageTracker:
     def _ensure_device(self, like: Optional[Tensor] = None) -> torch.device:
         if self._state is not None:
             return self._state["acc"].device
-        dev = _need_gpu("TriggeredAverageTracker", self.device or (like.device if like is not None else None))
+        dev = _stream.need_gpu("TriggeredAverageTracker", self.device or (like.device if like is not None else None))
         z = lambda *shape, dtype=torch.float64: torch.zeros(*shape, dtype=dtype, device=dev)  # noqa: E731
         self._state = {"acc": z(self.f_cols, self.n_lags, self.channels), "wsum": z(self.f_cols, self.n_lags),
                        "cnt": z(self.f_cols, self.n_lags, dtype=torch.int64), "sig_sum": z(self.channels),
@@ -136,67 +133,33 @@ class TriggeredAverageTracker:
         ``segments [rows]``, the utterance number of each row (negative: padding).  ``signal`` is float32 or bfloat16
         (anything else is converted to float32).  A tracker takes one of the two forms, not both.  Frames with
         ``frame_mask == 0`` are padding: they trigger nothing, end a run, and their signal is never read."""
-        if not (isinstance(code, (tuple, list)) and len(code) == 2):
-            raise TypeError("code must be a (values, indices) pair")
-        vals, idx = code
-        require_device_tensor(vals, "code values")
-        require_device_tensor(idx, "code indices")
-        require_device_tensor(signal, "signal")
-        if vals.shape != idx.shape or vals.dim() not in (2, 3):
-            raise ValueError(f"code: values {tuple(vals.shape)} and indices {tuple(idx.shape)} must share a [n_utt, T, k] or "
-                             f"[rows, k] shape")
-        k = vals.shape[-1]
-        if not 1 <= k <= N.STA_MAX_K:
-            raise ValueError(f"code: k must be in 1..{N.STA_MAX_K}, got {k}")
+        vals, idx, k = _stream.compact_code(code, "code", N.STA_MAX_K, also=((signal, "signal"),))
         if signal.shape != vals.shape[:-1] + (self.channels,):
             raise ValueError(f"signal must be {tuple(vals.shape[:-1]) + (self.channels,)} for this code, got {tuple(signal.shape)}")
         dev = self._ensure_device(vals)
         if vals.device != dev or signal.device != dev:
             raise N.WsaeError(f"the code is on {vals.device} and the signal on {signal.device}, the tracker on {dev}")
-        form = "numbered" if vals.dim() == 3 else "flat"
-        if self._form not in (None, form):
-            raise ValueError(f"this tracker has taken {self._form} updates: [n_utt, T, k] codes and flat codes with segments "
-                             f"cannot be mixed")
-        if vals.dim() == 3:
-            if segments is not None:
-                raise ValueError("a [n_utt, T, k] code numbers its utterances itself: pass segments only with a flat code")
-            n_utt, T = vals.shape[0], vals.shape[1]
-            seg = torch.arange(n_utt, dtype=torch.int32, device=dev)[:, None].expand(n_utt, T).reshape(-1)
-        else:
-            if segments is None:
-                raise ValueError("a flat [rows, k] code needs segments [rows]")
-            require_device_tensor(segments, "segments")
-            if segments.numel() != vals.shape[0]:
-                raise ValueError(f"segments has {segments.numel()} ids for {vals.shape[0]} rows")
-            seg = segments.detach().reshape(-1).to(device=dev, dtype=torch.int32)
+        form = _stream.take_form(self, vals)
+        seg, _ = _stream.frame_segments(vals, segments, frame_mask, dev)
         rows = seg.shape[0]
-        if frame_mask is not None:
-            require_device_tensor(frame_mask, "frame_mask")
-            if frame_mask.numel() != rows:
-                raise ValueError(f"frame_mask has {frame_mask.numel()} flags for {rows} frames")
-            seg = torch.where(frame_mask.detach().reshape(-1).to(dev) != 0, seg, torch.full_like(seg, -1))
         if rows > MAX_ROWS:
             raise N.WsaeError(f"TriggeredAverageTracker: {rows} frames in one update exceed {MAX_ROWS}")
         self._form = form
         if rows == 0:
             return
-        v = vals.detach().reshape(-1, k).to(torch.float32).contiguous()
-        i = idx.detach().reshape(-1, k).to(torch.int32).contiguous()
+        v, i = _stream.flat_code(vals, idx, k)
         y = signal.detach()
         if y.dtype not in (torch.float32, torch.bfloat16):
             y = y.to(torch.float32)
         if not (y.dim() == 2 and y.stride(1) == 1 and y.stride(0) >= self.channels):
             y = y.reshape(-1, self.channels).contiguous()
         ldy = y.stride(0) if rows > 1 else max(y.stride(0), self.channels)
-        seg = seg.contiguous()
         st = self._state
         with torch.cuda.device(dev):
             need = int(N.lib().wsae_sta_workspace_bytes(rows, k, self.hidden, self.f_lo, self.f_cols))
             if need < 0:
                 raise N.WsaeError(f"wsae_sta_workspace_bytes rejected rows = {rows}, k = {k}")
-            if self._ws is None or self._ws.numel() * 8 < need:
-                self._ws = None  # (release before the larger one is taken)
-                self._ws = torch.empty((need + 7) // 8, dtype=torch.int64, device=dev)
+            _stream.grow(self, (need + 7) // 8, torch.int64, dev)
             N.check(N.lib().wsae_sta_update(
                 v.data_ptr(), i.data_ptr(), k, self.hidden, seg.data_ptr(), rows, y.data_ptr(),
                 N.DT_BF16 if y.dtype == torch.bfloat16 else N.DT_F32, self.channels, ldy, self.lag_lo, self.lag_hi, self.f_lo,
@@ -283,9 +246,7 @@ def top_template_features(tracker, by: str = "contrast_peak", n: int = 20, min_c
     else:
         score = torch.where(cells > 0, (clean * clean).sum(1) / cells.clamp(min=1), nan)
     ok = (counts.reshape(z.shape[0], -1).amax(1) >= int(min_count)) & ~torch.isnan(score)
-    key = torch.where(ok, score, torch.full_like(score, float("-inf")))
-    order = torch.argsort(key, descending=True, stable=True)[:max(int(n), 0)]
-    order = order[ok[order]]
+    order = _stream.rank_features(score, ok, n)
     return order, score[order]
 
 
@@ -294,29 +255,19 @@ def collect_triggered_averages(model, utterances, *, device="cuda", **tracker_kw
     ``(x, signal, frame_mask [n_utt, T])``.  ``tracker_kw`` goes to ``TriggeredAverageTracker`` (the number of channels is
     read off the first signal).  The module must offer ``encode_compact`` (TopK and BatchTopK SAEs; a ReLU SAE's code is
     dense: ``TypeError``) and is run in eval mode; its previous mode is restored."""
-    if not hasattr(model, "encode_compact"):
-        raise TypeError(f"{type(model).__name__} has no compact code (encode_compact): triggered averages are for "
-                        f"TopK-family codes")
     tracker = None
-    mode = model.training
-    model.eval()
-    try:
-        with torch.no_grad():
-            for batch in utterances:
-                if not isinstance(batch, (tuple, list)) or len(batch) not in (2, 3):
-                    raise TypeError("an item must be (x, signal) or (x, signal, frame_mask)")
-                x, signal = batch[0], batch[1]
-                mask = batch[2] if len(batch) == 3 else None
-                if x.dim() != 3 or signal.dim() != 3:
-                    raise ValueError(f"x and signal must be [n_utt, T, .], got {tuple(x.shape)} and {tuple(signal.shape)}")
-                if tracker is None:
-                    tracker = TriggeredAverageTracker(model.hidden_dim, signal.shape[-1], device=device, **tracker_kw)
-                vals, idx = model.encode_compact(x.to(device))
-                shape = (x.shape[0], x.shape[1], vals.shape[-1])
-                tracker.update((vals.reshape(shape), idx.reshape(shape)), signal.to(device),
-                               frame_mask=None if mask is None else mask.to(device))
-    finally:
-        model.train(mode)
+    with _stream.encoding(model, hint="triggered averages are for TopK-family codes"):
+        for batch in utterances:
+            if not isinstance(batch, (tuple, list)) or len(batch) not in (2, 3):
+                raise TypeError("an item must be (x, signal) or (x, signal, frame_mask)")
+            x, signal = batch[0], batch[1]
+            mask = batch[2] if len(batch) == 3 else None
+            if x.dim() != 3 or signal.dim() != 3:
+                raise ValueError(f"x and signal must be [n_utt, T, .], got {tuple(x.shape)} and {tuple(signal.shape)}")
+            if tracker is None:
+                tracker = TriggeredAverageTracker(model.hidden_dim, signal.shape[-1], device=device, **tracker_kw)
+            tracker.update(_stream.utterance_code(model, x, device), signal.to(device),
+                           frame_mask=None if mask is None else mask.to(device))
     if tracker is None:
         raise ValueError("collect_triggered_averages: no utterances")
     return tracker
