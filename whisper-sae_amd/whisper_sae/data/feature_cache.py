@@ -124,6 +124,8 @@ class ActivationRing:
             raise N.WsaeError("push_layernorm takes hidden states that already live on the ring's device")
         if rows.dtype not in (torch.float32, torch.bfloat16):
             rows = rows.float()
+        if rows.shape[0] == 0:  # nothing to push (an empty tensor has no address to hand to the library)
+            return
         rows = rows.contiguous()
         w = weight.detach().to(device=self.device, dtype=torch.float32).contiguous()
         b = bias.detach().to(device=self.device, dtype=torch.float32).contiguous()
