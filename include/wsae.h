@@ -676,6 +676,58 @@ int wsae_sta_update(const float* vals, const int32_t* idx, int32_t k, int32_t hi
                     int32_t f_lo, int32_t f_cols, int32_t trigger, int32_t weight, double* acc, double* wsum, int64_t* cnt,
                     void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- activation profiles: value histograms and stratified samples ----------------------------------
+ * What the distribution of a feature's activations looks like, and examples drawn uniformly from every band of it,
+ * straight from a compact code vals / idx [n_rows, k] (as wsae_encode_topk writes them, 1 <= k <= WSAE_PROFILE_MAX_K).
+ * Ctx-free; the caller's stream, no allocation, no host synchronisation, no float atomics; argument errors are found on
+ * the host before any HIP call.  seg int32 [n_rows] (nullable = no padding): a row with seg < 0 is padding.  Feature f is
+ * active on a row iff the row is not padding and some entry has idx == f, v > 0 and 0 <= f < hidden (the rule of
+ * wsae_runs_update); an index repeated within a row counts once, with the value of its first active entry.  NaN is never
+ * active, +inf is.  The window is f_lo <= f < f_lo + f_cols; 0 <= n_rows <= 2^31 - 1 per call.
+ *
+ * wsae_profile_update.  With b the int32 bit pattern of an active value v, its bin is clamp((b >> 20) - 920, 0, 191):
+ * WSAE_PROFILE_BINS = 192 bins, eight per octave over [2^-12, 2^12); bin 8 e + s holds
+ * [2^(e-12) (1 + s/8), 2^(e-12) (1 + (s+1)/8)), bin 0 also everything below 2^-12 (denormals included) and bin 191
+ * everything from 4096 on.  State (caller-owned device memory, zero-initialised except min_bits), per feature of the
+ * window: fires int32 (the rows on which it was active), hist int32 [f_cols, 192], max_bits int32 (the maximum of b;
+ * positive floats order as their bits), min_bits int32 (the minimum; initialise to 0x7f800000), over int32 (values
+ * >= 4096), sum_q int64 (the sum of rint(min(v, 4096) 2^20): the product is exact in fp32, the conversion rounds to
+ * nearest even; a term is at most 2^32, so 2^31 - 1 rows cannot overflow it); total_rows int64 [1] += the non-padding
+ * rows.  Every field is an integer sum, minimum or maximum: the state does not depend on the launch geometry, on the
+ * order of the calls or on the batching, and two states merge by add / min / max.  Workspace:
+ * wsae_profile_workspace_bytes, 0 for valid arguments in this form (NULL is accepted then) and -1 for invalid ones.
+ *
+ * wsae_sample_update.  Row r of the call has the ordinal ord_base + r (0 <= ord_base, ord_base + n_rows <= 2^31; padding
+ * rows take their ordinal too).  edges fp32 [f_cols, n_strata - 1], ascending per feature of the window (1 <= n_strata <=
+ * WSAE_SAMPLE_MAX_STRATA; NULL allowed when n_strata == 1): the stratum of an active (row, f, v) is the number of f's
+ * edges that are <= v.  Its priority, in uint32 arithmetic with o the ordinal:
+ *     x = o * 0x9E3779B1 ^ f * 0x85EBCA77 ^ seed;  x ^= x >> 16;  x *= 0x85EBCA6B;  x ^= x >> 13;  x *= 0xC2B2AE35;
+ *     x ^= x >> 16
+ * (f is the feature's index in [0, hidden), not its column in the window) and its key is (uint64) x << 32 | o, unique
+ * within a feature.  State per list (feature of the window, stratum): keys uint64 [f_cols, n_strata, keep] ascending,
+ * an unused slot = 2^64 - 1 (the caller initialises them so; no key reaches it); svals fp32 [f_cols, n_strata, keep],
+ * the values beside the keys, 0 in an unused slot; seen int32 [f_cols, n_strata] += every active entry of the stratum,
+ * sampled or not (1 <= keep <= WSAE_SAMPLE_MAX_KEEP).  After any sequence of calls a list holds the `keep` smallest keys
+ * ever offered to it: a uniform sample without replacement of the stratum that does not depend on call order, batching
+ * or launch geometry, and two states over disjoint ordinals merge exactly (union, keep the smallest).  At most
+ * 2^31 - 1 entries (n_rows k) per call and fewer than 2^31 - 1 lists (f_cols n_strata).  Workspace (8-byte aligned): wsae_sample_workspace_bytes - three int32 vectors
+ * over the lists and 12 bytes per entry; -1 for invalid arguments; contents arbitrary on entry. */
+#define WSAE_PROFILE_MAX_K 128
+#define WSAE_PROFILE_BINS 192
+#define WSAE_SAMPLE_MAX_STRATA 16
+#define WSAE_SAMPLE_MAX_KEEP 64
+int64_t wsae_profile_workspace_bytes(int64_t n_rows, int32_t k, int32_t hidden, int32_t f_lo, int32_t f_cols);
+int wsae_profile_update(const float* vals, const int32_t* idx, int32_t k, int32_t hidden, const int32_t* seg, int64_t n_rows,
+                        int32_t f_lo, int32_t f_cols, int32_t* fires, int32_t* hist, int32_t* max_bits, int32_t* min_bits,
+                        int32_t* over, int64_t* sum_q, int64_t* total_rows, void* workspace, int64_t workspace_bytes,
+                        void* stream);
+int64_t wsae_sample_workspace_bytes(int64_t n_rows, int32_t k, int32_t hidden, int32_t f_lo, int32_t f_cols, int32_t n_strata,
+                                    int32_t keep);
+int wsae_sample_update(const float* vals, const int32_t* idx, int32_t k, int32_t hidden, const int32_t* seg, int64_t n_rows,
+                       int64_t ord_base, int32_t f_lo, int32_t f_cols, const float* edges, int32_t n_strata, int32_t keep,
+                       uint32_t seed, uint64_t* keys, float* svals, int32_t* seen, void* workspace, int64_t workspace_bytes,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif
