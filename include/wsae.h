@@ -469,7 +469,10 @@ int wsae_ctx_set_relu_fp8(wsae_ctx* ctx, int32_t on);
  * bf16 in the ctx workspace, written by the encoder GEMM's epilogue, and `hidden` may be NULL - a trainer that never looks at
  * it saves 4 B H bytes of stores per step; a non-NULL `hidden` still receives the fp32 copy).  Where this returns 0, `recon` is
  * optional as well: the forward's residual pass already leaves g = 2 (recon - x) / (B cols) and the db_d partials for the
- * backward of the same batch, which then needs no recon (a non-NULL `recon` still receives the fp32 reconstruction). */
+ * backward of the same batch, which then needs no recon (a non-NULL `recon` still receives the fp32 reconstruction).
+ * One exception: wsae_decode_loss / wsae_encode_decode on the same ctx between that forward and its backward take the
+ * buffers g and the db_d partials live in (and nothing else the backward reads, as long as the batch is the same); the
+ * backward then rebuilds both from `recon`, bit for bit, and returns an error when `recon` is NULL. */
 int wsae_relu_needs_hidden(const wsae_ctx* ctx, int32_t B);
 /* Per-feature weights w[hidden_dim] of the L1 term (device memory, caller-owned, must outlive the calls; NULL = all ones, the
  * default): the sparsity term of wsae_relu_forward becomes sum_b sum_s w[s] |hidden[b][s]| / (B H) and wsae_relu_backward adds

@@ -522,7 +522,7 @@ slab_sum_kernel(const float* __restrict__ slabs, int64_t slab_stride, int nz, in
 // The same sum with every slab's load of an element in flight at once (the loop above issues them one dependent trip at a
 // time), one float4 per thread and pass, and the block's sum of squares left as a global-norm partial: the optimizer then
 // needs no norm pass over the matrices (wsae_adamw_step norm_from_wgrad = 1; the bias gradients' squares are added by
-// bias_sq_kernel below).  nz <= 8.
+// the last block of colsum2_kernel).  nz <= 8.
 __global__ void __launch_bounds__(256)
 slab_sum8_kernel(const float* __restrict__ slabs, int64_t slab_stride, int nz, int64_t n4, float* __restrict__ grads,
                  float* __restrict__ g_bpre, int D, float* __restrict__ part_sq) {
@@ -545,17 +545,6 @@ slab_sum8_kernel(const float* __restrict__ slabs, int64_t slab_stride, int nz, i
         for (int d = threadIdx.x; d < D; d += 256) g_bpre[d] = 0.f;  // no pre-bias in this module: it stays exactly 0
     const float t = block_sum(sq, red);
     if (threadIdx.x == 0) part_sq[blockIdx.x] = t;
-}
-
-// squares of the two bias gradients (H + D values) as one more norm partial
-__global__ void __launch_bounds__(1024) bias_sq_kernel(const float* __restrict__ a, int na, const float* __restrict__ b, int nb,
-                                                       float* __restrict__ out) {
-    __shared__ float red[16];
-    float sq = 0.f;
-    for (int i = threadIdx.x; i < na; i += 1024) sq = fmaf(a[i], a[i], sq);
-    for (int i = threadIdx.x; i < nb; i += 1024) sq = fmaf(b[i], b[i], sq);
-    const float t = block_sum(sq, red);
-    if (threadIdx.x == 0) *out = t;
 }
 
 int check_dims(wsae_ctx* ctx, int B, const char* who) {
