@@ -184,7 +184,10 @@ int wsae_encode_decode(wsae_ctx* ctx, const float* params, const void* x, int32_
  * [H,B]x[B,D] contractions on MFMA with the sparse operand rebuilt in LDS from the compact code,
  * plus the three bias gradients.  Needs the g left in ctx by wsae_decode_loss(want_bwd=1) on the
  * same batch, and the SAME x / x_dtype / rows as that forward (a bf16 batch in BF16 mode is not staged by the
- * forward: this call transposes it for the dW_e contraction).  grads: flat pack, overwritten. */
+ * forward: this call transposes it for the dW_e contraction).  grads: flat pack, overwritten.
+ * In BF16 mode with input_dim > 256 behind the MFMA decode launch the code is contracted on the 2:4 sparse MFMA
+ * (v_smfmac_f32_32x32x32_bf16: exact for every code, deterministic).  WSAE_WGRAD_SPARSE=0 in the
+ * environment at wsae_ctx_create time keeps the dense form (A/B runs and tests); the two differ in the last bits. */
 int wsae_weight_grads(wsae_ctx* ctx, const float* params, const void* x, int32_t x_dtype,
                       const int32_t* rows, const float* vals, const int32_t* idx,
                       const float* dpre, int32_t B, float* grads, void* stream);

@@ -13,14 +13,16 @@ for r in range(rounds):
     for tag, lib in (("A", a), ("B", b)):
         env = dict(os.environ, WSAE_LIB=os.path.abspath(lib))
         o = subprocess.run([sys.executable, "bench.py", "--full", "--no-cpu-baseline", "--steps", "100", "--warmup", "100", "--profile-all"],
-                           env=env, capture_output=True, text=True)
+                           env=env, capture_output=True, text=True, timeout=300)
         line = [l for l in o.stdout.splitlines() if l.startswith("{")]
-        if not line:
-            print(tag, "FAILED", o.stderr[-800:]); continue
+        if not line:  # (nothing more is started on the GPU after a run that failed)
+            print(tag, "FAILED", o.returncode, o.stderr[-800:]); sys.exit(1)
         j = json.loads(line[-1])
         k = {n.split("<")[0].replace("_kernel", ""): round(v * 1e3, 1) for n, v in j["kernel_ms_per_step"].items()}
         o2 = subprocess.run([sys.executable, "bench.py", "--full", "--no-cpu-baseline", "--steps", "100", "--warmup", "100"],
-                            env=env, capture_output=True, text=True)
+                            env=env, capture_output=True, text=True, timeout=300)
+        if o2.returncode != 0:
+            print(tag, "FAILED", o2.returncode, o2.stderr[-800:]); sys.exit(1)
         j2 = json.loads([l for l in o2.stdout.splitlines() if l.startswith("{")][-1])
         print(tag, "step_us", round(j2["ms_per_step"] * 1e3, 1), "loss", j2["final_loss"], k, flush=True)
 PY

@@ -93,6 +93,8 @@ struct wsae_ctx {
     uint32_t* tmin;       // three groups of minimum slots (wsae_topk.h, TG_GROUP_WORDS each) in rotation, then the count of rows that recomputed strips
     int tmin_cur;         // slot the current batch's TopK launch fills (the GEMM read the other two)
     int strip_predict;    // 1 (default): the encoder GEMM of encode_topk stores strips selectively
+    int wgrad_sparse;     // 1 (default): the bf16 row-major weight-gradient contraction runs the TopK code through the 2:4 sparse MFMA
+                          // (wgrad2s_kernel); 0 (WSAE_WGRAD_SPARSE=0 when the context is created): the dense form (wgrad2_kernel)
     float tg_fixed_s;     // > 0: fixed margin s of the store threshold instead of the adaptive one (WSAE_STRIP_SAFETY, experiments)
     int pred_valid;       // 1: pre holds only the strips above the threshold; the TopK launch must check rows against it
     const void* pred_x;   // that GEMM's A operand and row list (what a row recomputes its missing strips from)

@@ -166,6 +166,8 @@ extern "C" int wsae_ctx_create(const wsae_config* cfg, wsae_ctx** out) {
     c->btk_ws = (int32_t*)(base + o_bt);
     const char* sp = getenv("WSAE_STRIP_PREDICT");  // (A/B runs: "0" creates contexts with the selective strip stores off)
     c->strip_predict = (sp && sp[0] == '0') ? 0 : 1;
+    const char* ws = getenv("WSAE_WGRAD_SPARSE");  // (A/B runs and tests: "0" keeps the dense weight-gradient contraction)
+    c->wgrad_sparse = (ws && ws[0] == '0') ? 0 : 1;
     const char* ss = getenv("WSAE_STRIP_SAFETY");
     c->tg_fixed_s = ss ? (float)atof(ss) : 0.f;
     c->ws_bytes = cv.total;

@@ -357,7 +357,100 @@ struct Mfma96<bf16_t, MI> {
         }
         }
     }
+    // 2:4 sparse form of the row-major slab (wgrad2s_kernel): the left operand is COMPRESSED, two K = 32 steps of
+    // v_smfmac_f32_32x32x32_bf16 per 64-row chunk instead of four dense K = 16 steps.  Operand semantics as measured by
+    // profiles/tools/probe_smfmac.hip (profiles/wgrad2_sparse_probe.txt): of the 32 k of a step, lane l's 8 values are two
+    // kept values for each of the 4-k groups at k = 8 h, 8 h + 4, 16 + 8 h, 16 + 8 h + 4 (h = l >> 5: the dense 32x32x16
+    // map, twice), the 2-bit position of value s in bits [2 s + 1 : 2 s] of the index register (ABID = 0: bits 15:0); its 16 B
+    // values are k = 16 h .. 16 h + 15.  A zero value may carry any position.
+    //   As: the value image, 128 bytes per feature = [layer 0 | layer 1] x 4 fragments of 16 bytes (fragment 2 t + h = what
+    //       a lane of half h feeds step t), chunk c at slot c ^ ((row >> 1) & 7) as every swizzled image here, so the
+    //       fragment reads are conflict-free for the reason given at swz_off;
+    //   Ix: the index image, uint32 [layer][step][NF features]: bits 15:0 for h = 0, 31:16 for h = 1 (32 consecutive words
+    //       per read, both halves the same address: conflict-free);
+    //   Bs: the row-major dense image as in slab<RM = true>; a B fragment is FOUR ds_read_b64_tr_b16 (4-row blocks q4 = 0..3
+    //       of the half's 16 batch rows), so a 2:4 group is four consecutive batch rows.  Per 16-lane group these are the
+    //       reads of the dense form (q4 = 0, 1 those of its h = 0 lanes, q4 = 2, 3 those of its h = 1 lanes): conflict-free.
+    //   m2: bit mi set = feature block mi of this wave has entries in layer 1 (a third or fourth entry of some 4-row
+    //       group); wave-uniform.  Layer 1 is multiplied in a second pass, only for those blocks.
+    // The B fragments stream through two register sets (one column tile ahead); the A fragments of step 1 are requested
+    // behind the last MFMAs of step 0.  between(0..2) as in slab(), after the first, second and fourth column group.
+    template <int NF, typename F>
+    static __device__ __forceinline__ void slab_sparse(const char* As, const uint32_t* Ix, uint32_t Bs, int a_row0, int b_row0,
+                                                       int lane, uint32_t m2, f32x16 (&acc)[MI][3], F&& between) {
+        typedef __bf16 bf16x16 __attribute__((ext_vector_type(16)));
+        typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4_t;
+        const int r = lane & 31, h = lane >> 5;
+        const int sw = (r >> 1) & 7;
+        const char* ap = As + (a_row0 + r) * SWZ_ROW_BYTES;
+        const uint32_t* ip = Ix + a_row0 + r;
+        const int i = lane & 15, g1 = (lane >> 4) & 1;
+        auto load_a = [&](int layer, int t, int mi) -> bf16x8 {
+            return *(const bf16x8*)(ap + mi * 32 * SWZ_ROW_BYTES + (((layer * 4 + t * 2 + h) ^ sw) << 4));
+        };
+        auto load_ix = [&](int layer, int t, int mi) -> int { return (int)(ip[(layer * 2 + t) * NF + mi * 32] >> (16 * h)); };
+        // B addresses: one register per column tile.  Block q4 = 0 of step 0 is row 16 h + (i >> 2), whose swizzle is
+        // ((i >> 3) & 1) << 2; block q4 is 4 q4 rows further and its swizzle differs by q4 in the low slot bits, step t is 32
+        // rows further with the same swizzle.  The image is 128-byte aligned in LDS (Bs is an LDS byte address), so the slot
+        // is bits 6:4 of the address itself: block q4 = (address ^ (q4 << 4)) + 512 q4 + 4096 t, the sums instruction offsets.
+        uint32_t tb[3];
+#pragma unroll
+        for (int ni = 0; ni < 3; ++ni) {
+            const int c0 = b_row0 + ni * 32 + g1 * 16 + 4 * (i & 3);  // first of this lane's 4 address columns
+            tb[ni] = Bs + (c0 >> 6) * 8192 + (16 * h + (i >> 2)) * 128 + ((((c0 & 63) >> 3) ^ (((i >> 3) & 1) << 2)) << 4) + 8 * (i & 1);
+        }
+        auto load_b = [&](int t, int ni) -> bf16x16 {
+            bf16x4 q[4];
+#pragma unroll
+            for (int q4 = 0; q4 < 4; ++q4)
+                q[q4] = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_t*)(uintptr_t)((tb[ni] ^ (uint32_t)(q4 << 4)) + 512 * q4 + 4096 * t));
+            const bf16x8 lo = __builtin_shufflevector(q[0], q[1], 0, 1, 2, 3, 4, 5, 6, 7);
+            const bf16x8 hi = __builtin_shufflevector(q[2], q[3], 0, 1, 2, 3, 4, 5, 6, 7);
+            return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15);
+        };
+        bf16x8 a[MI];
+        int ix[MI];
+        bf16x16 b[2];
+#pragma unroll
+        for (int mi = 0; mi < MI; ++mi) {
+            a[mi] = load_a(0, 0, mi);
+            ix[mi] = load_ix(0, 0, mi);
+        }
+        b[0] = load_b(0, 0);
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {  // (step, column tile) = (j / 3, j % 3)
+            if (j < 5) b[(j + 1) & 1] = load_b((j + 1) / 3, (j + 1) % 3);
+#pragma unroll
+            for (int mi = 0; mi < MI; ++mi)
+                acc[mi][j % 3] = __builtin_amdgcn_smfmac_f32_32x32x32_bf16(a[mi], b[j & 1], acc[mi][j % 3], ix[mi], 0, 0);
+            if (j == 2) {
+#pragma unroll
+                for (int mi = 0; mi < MI; ++mi) {
+                    a[mi] = load_a(0, 1, mi);
+                    ix[mi] = load_ix(0, 1, mi);
+                }
+            }
+            if (j == 0) between(0);
+            if (j == 1) between(1);
+            if (j == 3) between(2);
+        }
+        if (m2) {
+#pragma unroll
+            for (int t = 0; t < 2; ++t)
+#pragma unroll
+                for (int mi = 0; mi < MI; ++mi) {
+                    if (!((m2 >> mi) & 1)) continue;
+                    const bf16x8 a2 = load_a(1, t, mi);
+                    const int i2 = load_ix(1, t, mi);
+#pragma unroll
+                    for (int ni = 0; ni < 3; ++ni)
+                        acc[mi][ni] = __builtin_amdgcn_smfmac_f32_32x32x32_bf16(a2, load_b(t, ni), acc[mi][ni], i2, 0, 0);
+                }
+        }
+    }
     // row sums of the 16-row tile at row0 (+= over the chunk), every column of rs holds them
+    // (on the compressed value image of slab_sparse the same call sums the kept values of both layers: positions do not
+    // matter for a sum)
     static __device__ __forceinline__ void rowsum16(const char* As, int row0, int lane, f32x4& rs) {
         const int r = row0 + (lane & 15), q = lane >> 4;
         bf16x8 ones;

@@ -418,6 +418,64 @@ wgrad_kernel(const uint32_t* __restrict__ ent_pos, const T* __restrict__ ent_hid
 // different 64-byte halves of it (bit 2 of the slot), so the transposed reads are conflict-free.
 __device__ __forceinline__ int rm_swz(int r) { return (((r >> 1) & 1) << 2) | ((r >> 2) & 3); }
 
+// The tail of wgrad2_kernel and wgrad2s_kernel: a workgroup's 192 x 384 accumulator tile into its split-K slab, and the db_e row sums.
+__device__ __forceinline__ void w2_epilogue(char* smem, const f32x16 (&acc)[W2_MI][3], const f32x4& rs0, const f32x4& rs1,
+                                            float* __restrict__ out, float* __restrict__ dbe_slab, int which, int split, int f0, int d0,
+                                            int wm, int wn, int wave, int lane, int H, int D, int nslots, int dec_row_base, bool do_dbe) {
+    // slab layout [row][slot][D] (nslots slots per row: the partial rows grad_finish sums are one contiguous run); rows
+    // [0, H) = dW_e, the dW_dT rows start at dec_row_base (H when one launch holds both matrices, 0 when it holds one)
+    const int64_t rstr = (int64_t)nslots * D;
+    float* dst = out + (which == 0 ? (int64_t)dec_row_base * rstr : 0) + (int64_t)split * D;
+    const int col = lane & 31, rq = lane >> 5;
+    if (f0 + W2_M <= H && d0 + W2_N <= D) {
+        // Interior tiles: the accumulators go through an LDS patch (the stages are free now) and leave as 16-byte stores,
+        // 36 store instructions per wave instead of 144 four-byte ones.  The tail of this kernel is bound by the number
+        // of store instructions, not by their bytes (bf16 slabs - half the bytes, same instructions - did not move it).
+        constexpr int PSW = 100;  // floats per patch row: 96 + 4 (16-byte aligned rows, conflict-free column writes)
+        float* patch = (float*)smem + wave * 32 * PSW;
+        float* drow = dst + (int64_t)(f0 + wm * 32 * W2_MI) * rstr + d0 + wn * 96;
+#pragma unroll
+        for (int mi = 0; mi < W2_MI; ++mi) {
+#pragma unroll
+            for (int ni = 0; ni < 3; ++ni)
+#pragma unroll
+                for (int r = 0; r < 16; ++r)
+                    patch[((r & 3) + 8 * (r >> 2) + 4 * rq) * PSW + ni * 32 + col] = acc[mi][ni][r];
+            __builtin_amdgcn_wave_barrier();
+#pragma unroll
+            for (int i = 0; i < 12; ++i) {
+                const int idx = lane + 64 * i;      // float4 number inside the 32 x 96 patch
+                const int row = idx / 24, c4 = idx - row * 24;
+                const float4 v = *(const float4*)(patch + row * PSW + c4 * 4);
+                *(float4*)(drow + (int64_t)(mi * 32 + row) * rstr + c4 * 4) = v;
+            }
+            __builtin_amdgcn_wave_barrier();
+        }
+    } else {
+#pragma unroll
+        for (int mi = 0; mi < W2_MI; ++mi)
+#pragma unroll
+            for (int ni = 0; ni < 3; ++ni) {
+                const int d = d0 + wn * 96 + ni * 32 + col;
+                if (d >= D) continue;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int f = f0 + wm * 32 * W2_MI + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * rq;
+                    if (f < H) dst[(int64_t)f * rstr + d] = acc[mi][ni][r];
+                }
+            }
+    }
+    if (do_dbe && (lane & 15) == 0) {  // column 0 of the ones product = the row sums
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int fa = f0 + wave * 16 + 4 * (lane >> 4) + j;
+            if (fa < H) dbe_slab[(int64_t)split * H + fa] = rs0[j];
+            const int fb = f0 + (wave + W2_WAVES) * 16 + 4 * (lane >> 4) + j;
+            if (wave + W2_WAVES < W2_M / 16 && fb < H) dbe_slab[(int64_t)split * H + fb] = rs1[j];
+        }
+    }
+}
+
 template <typename T, bool RM>
 __global__ void __launch_bounds__(W2_THREADS)
 wgrad2_kernel(const uint32_t* __restrict__ ent_pos, const T* __restrict__ ent_hid, const T* __restrict__ ent_dpre,
@@ -571,58 +629,227 @@ wgrad2_kernel(const uint32_t* __restrict__ ent_pos, const T* __restrict__ ent_hi
         __syncthreads();
     }
 
-    // slab layout [row][slot][D] (nslots slots per row: the partial rows grad_finish sums are one contiguous run); rows
-    // [0, H) = dW_e, the dW_dT rows start at dec_row_base (H when one launch holds both matrices, 0 when it holds one)
-    const int64_t rstr = (int64_t)nslots * D;
-    float* dst = out + (which == 0 ? (int64_t)dec_row_base * rstr : 0) + (int64_t)split * D;
-    const int col = lane & 31, rq = lane >> 5;
-    if (f0 + W2_M <= H && d0 + W2_N <= D) {
-        // Interior tiles: the accumulators go through an LDS patch (the stages are free now) and leave as 16-byte stores,
-        // 36 store instructions per wave instead of 144 four-byte ones.  The tail of this kernel is bound by the number
-        // of store instructions, not by their bytes (bf16 slabs - half the bytes, same instructions - did not move it).
-        constexpr int PSW = 100;  // floats per patch row: 96 + 4 (16-byte aligned rows, conflict-free column writes)
-        float* patch = (float*)smem + wave * 32 * PSW;
-        float* drow = dst + (int64_t)(f0 + wm * 32 * W2_MI) * rstr + d0 + wn * 96;
+    w2_epilogue(smem, acc, rs0, rs1, out, dbe_slab, which, split, f0, d0, wm, wn, wave, lane, H, D, nslots, dec_row_base, do_dbe);
+}
+
+// ------------------------------------------------------------------------------------------------
+// wgrad2s_kernel: wgrad2_kernel<bf16, RM = true> with the TopK code contracted on the 2:4 sparse MFMA
+// (v_smfmac_f32_32x32x32_bf16, Mfma96::slab_sparse): half the matrix instructions and half the left-operand fragment
+// reads per chunk.  Geometry, split-K, XCD mapping, dense image, LDS-DMA, slab layout and epilogue are wgrad2_kernel's.
+//
+// The left operand of a stage is a COMPRESSED image in place of the 192 x 64 dense slice.  A 2:4 group is one feature x
+// four consecutive batch rows (rows 4 g .. 4 g + 3 of the chunk, g = 0..15).  An entry's slot is its rank among the
+// entries of its group in ascending row order: ranks 0, 1 go to layer 0, ranks 2, 3 to layer 1 (two 2:4 layers hold 4 of
+// 4, so every code is represented exactly; layer 1 is multiplied only for the 32-feature blocks that have it).  Per stage:
+//   values  [192 features][128 bytes] (the former dense slice's place and swizzle): chunk layer * 4 + 2 t + hh holds what a
+//           lane of half hh feeds K step t = rows 32 t + {8 hh .. 8 hh + 7, 16 + 8 hh .. 16 + 8 hh + 7}: four groups x 2
+//           slots of bf16;
+//   index   uint32 [layer][t][192]: 2-bit row-in-group of slot s of half hh at bits 16 hh + 2 s;
+//   mask    one word, bit = 32-feature block with entries in layer 1.
+// The rank comes from a bitmap of one nibble per (feature, group), bit = row in group, three of them in rotation: in the
+// window between the two barriers of chunk c the entries of chunk c + 2 set their bits (integer LDS OR), the entries of
+// chunk c + 1 - whose bits were set one window earlier, and whose nibble was read at the top of chunk c, rank = popcount
+// of the lower bits - write value and index, and the entries of chunk c store zeros over their cells, index words and
+// bitmap words (all writers of a word write 0).  The three bitmaps and the two stages keep those three accesses on
+// different words, so the window needs no ordering inside it; nothing depends on the order of the entries in the sorted
+// arrays, and no sum changes its order from launch to launch.  The entry prefetch therefore runs two chunks ahead
+// (positions) and one chunk ahead (values).
+// LDS: 2 x (24 + 48) KB + 2 x 3 KB index + 3 x 1.5 KB bitmaps + masks = 154.5 KB of the CU's 160.
+// ------------------------------------------------------------------------------------------------
+#define W2S_IX_BYTES (2 * 2 * W2_M * 4)
+#define W2S_BM_BYTES (W2_M * 2 * 4)
+#define W2S_IX_OFF (2 * W2_STAGE)
+#define W2S_BM_OFF (W2S_IX_OFF + 2 * W2S_IX_BYTES)
+#define W2S_MASK_OFF (W2S_BM_OFF + 3 * W2S_BM_BYTES)
+#define W2S_LDS_BYTES (W2S_MASK_OFF + 16)
+static_assert(W2S_LDS_BYTES <= 160 * 1024, "wgrad2s_kernel: the stages do not fit the LDS of a CU");
+
+__global__ void __launch_bounds__(W2_THREADS)
+wgrad2s_kernel(const uint32_t* __restrict__ ent_pos, const bf16_t* __restrict__ ent_hid, const bf16_t* __restrict__ ent_dpre,
+               const int32_t* __restrict__ ent_off, const bf16_t* __restrict__ xT, const bf16_t* __restrict__ gT, int B, int H,
+               int D, int nsplit, int ntm, int ntn, float* __restrict__ out, float* __restrict__ dbe_slab,
+               const int32_t* __restrict__ xrows, int which0, int nslots, int dec_row_base) {
+    typedef bf16_t T;
+    extern __shared__ __attribute__((aligned(1024))) char smem[];  // (slab_sparse takes swizzle bits from LDS addresses)
+    constexpr int KT = 64, EPC = 8;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 2, wn = wave & 3;
+    const int split = blockIdx.x % nsplit;
+    int tile = blockIdx.x / nsplit;
+    const int which = which0 + tile / (ntm * ntn);  // 0: dW_dT (hidden, g)   1: dW_e (dpre, x_c)
+    tile -= (which - which0) * ntm * ntn;
+    const int tm = tile / ntn, tn = tile % ntn;
+    const int f0 = tm * W2_M, d0 = tn * W2_N;
+    const T* Bt = which == 0 ? gT : xT;  // [B][D] row-major (x: indexed through xrows when given)
+    const T* sv = which == 0 ? ent_hid : ent_dpre;
+    const bool do_dbe = (which == 1) && (tn == 0);
+
+    const int nchunks = (B + KT - 1) / KT;
+    const int per = (nchunks + nsplit - 1) / nsplit;
+    const int c_begin = split * per, c_end = min(nchunks, c_begin + per);
+
+    f32x16 acc[W2_MI][3];
 #pragma unroll
-        for (int mi = 0; mi < W2_MI; ++mi) {
+    for (int i = 0; i < W2_MI; ++i)
 #pragma unroll
-            for (int ni = 0; ni < 3; ++ni)
+        for (int j = 0; j < 3; ++j)
 #pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    patch[((r & 3) + 8 * (r >> 2) + 4 * rq) * PSW + ni * 32 + col] = acc[mi][ni][r];
-            __builtin_amdgcn_wave_barrier();
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    f32x4 rs0 = {0.f, 0.f, 0.f, 0.f}, rs1 = {0.f, 0.f, 0.f, 0.f};
+
+    // the dense operand's LDS-DMA: as wgrad2_kernel<T, true>
+    const int dma_r = lane >> 3, dma_s = lane & 7;
+    const uint32_t smem_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
+    const T* rm_src = Bt;
+    int rm_b = 0;
+    const int rm_c = (dma_s ^ rm_swz(wave * 8 + dma_r)) * EPC;
+    auto rm_row = [&](int ck) {
+        const int b = min(ck * KT + wave * 8 + dma_r, B - 1);
+        rm_b = (which == 1 && xrows) ? xrows[b] : b;
+    };
+    auto rm_use = [&]() { rm_src = Bt + (int64_t)rm_b * D; };
+    auto dma3 = [&](int stage, int j0) {
 #pragma unroll
-            for (int i = 0; i < 12; ++i) {
-                const int idx = lane + 64 * i;      // float4 number inside the 32 x 96 patch
-                const int row = idx / 24, c4 = idx - row * 24;
-                const float4 v = *(const float4*)(patch + row * PSW + c4 * 4);
-                *(float4*)(drow + (int64_t)(mi * 32 + row) * rstr + c4 * 4) = v;
-            }
-            __builtin_amdgcn_wave_barrier();
+        for (int j = j0; j < j0 + W2_PIECES / 2; ++j) {
+            const int dcol = min(d0 + j * 64 + rm_c, D - EPC);
+            glds16(rm_src + dcol, smem_lds + stage * W2_STAGE + W2_A_BYTES + j * 8192 + wave * 1024);
         }
-    } else {
-#pragma unroll
-        for (int mi = 0; mi < W2_MI; ++mi)
-#pragma unroll
-            for (int ni = 0; ni < 3; ++ni) {
-                const int d = d0 + wn * 96 + ni * 32 + col;
-                if (d >= D) continue;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int f = f0 + wm * 32 * W2_MI + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * rq;
-                    if (f < H) dst[(int64_t)f * rstr + d] = acc[mi][ni][r];
-                }
-            }
-    }
-    if (do_dbe && (lane & 15) == 0) {  // column 0 of the ones product = the row sums
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int fa = f0 + wave * 16 + 4 * (lane >> 4) + j;
-            if (fa < H) dbe_slab[(int64_t)split * H + fa] = rs0[j];
-            const int fb = f0 + (wave + W2_WAVES) * 16 + 4 * (lane >> 4) + j;
-            if (wave + W2_WAVES < W2_M / 16 && fb < H) dbe_slab[(int64_t)split * H + fb] = rs1[j];
+    };
+
+    uint32_t* const ix_img = (uint32_t*)(smem + W2S_IX_OFF);    // [stage][layer][t][192]
+    uint32_t* const bm_img = (uint32_t*)(smem + W2S_BM_OFF);    // [3][192][2]
+    uint32_t* const l2mask = (uint32_t*)(smem + W2S_MASK_OFF);  // [stage]
+    // entry p = feature << 16 | row: the bitmap word of its group, and the nibble's shift in it
+    auto bm_word = [&](int bm, uint32_t p) -> uint32_t* { return bm_img + bm * (W2S_BM_BYTES / 4) + (p >> 16) * 2 + ((p >> 5) & 1); };
+    auto setbit = [&](int bm, uint32_t p) { atomicOr(bm_word(bm, p), 1u << (((p >> 2) & 7) * 4 + (p & 3))); };
+    // the entry with its rank in bits 9:8 (free: the row takes 6 bits).  The bitmap of a chunk is complete one window before
+    // its scatter, so the register entry is ranked at the top of the chunk, its LDS read landing under the MFMA phase
+    auto ranked = [&](int bm, uint32_t p) -> uint32_t {
+        const int row = (int)(p & 63u);
+        const uint32_t nib = (*bm_word(bm, p) >> (((row >> 2) & 7) * 4)) & 15u;
+        return p | ((uint32_t)__builtin_popcount(nib & ((1u << (row & 3)) - 1u)) << 8);
+    };
+    auto put = [&](int stage, uint32_t p, T v) {  // p: ranked
+        const int f = (int)(p >> 16), row = (int)(p & 63u);
+        const int t = row >> 5, grp = (row >> 2) & 7, bit = row & 3;
+        const int rank = (int)((p >> 8) & 3u);
+        const int layer = rank >> 1, slot = rank & 1;
+        const int hh = (grp >> 1) & 1, j = (grp & 1) + 2 * (grp >> 2);  // probe_smfmac: the groups a lane of half hh feeds step t
+        *(T*)(smem + stage * W2_STAGE + swz_off(f, layer * 4 + t * 2 + hh) + j * 4 + slot * 2) = v;
+        atomicOr(ix_img + stage * (W2S_IX_BYTES / 4) + (layer * 2 + t) * W2_M + f, (uint32_t)bit << (16 * hh + 4 * j + 2 * slot));
+        if (layer) atomicOr(l2mask + stage, 1u << (f >> 5));
+    };
+    auto clear = [&](int stage, int bm, uint32_t p, bool l2) {  // every store is a zero: entries that share a word do not race
+        const int f = (int)(p >> 16), row = (int)(p & 63u);
+        const int t = row >> 5, grp = (row >> 2) & 7;
+        const int hh = (grp >> 1) & 1, j = (grp & 1) + 2 * (grp >> 2);
+        *(uint32_t*)(smem + stage * W2_STAGE + swz_off(f, t * 2 + hh) + j * 4) = 0u;
+        ix_img[stage * (W2S_IX_BYTES / 4) + t * W2_M + f] = 0u;
+        if (l2) {
+            *(uint32_t*)(smem + stage * W2_STAGE + swz_off(f, 4 + t * 2 + hh) + j * 4) = 0u;
+            ix_img[stage * (W2S_IX_BYTES / 4) + (2 + t) * W2_M + f] = 0u;
         }
+        *bm_word(bm, p) = 0u;
+    };
+
+    // entry ranges: p = the chunk the MFMAs work on (cleared afterwards), e = the next one (scattered in this chunk's
+    // window), f = the one after that (sets its bitmap bits in this window), n = offsets only, one chunk further
+    int p_lo = 0, p_n = 0, e_lo = 0, e_n = 0, f_lo = 0, f_n = 0, n_lo = 0, n_n = 0;
+    uint32_t p_pos = 0, e_pos = 0, f_pos = 0;
+    T e_val = (T)0.f;
+    auto offsets = [&](int ck) {
+        const int32_t* o = ent_off + (int64_t)min(ck, nchunks - 1) * (ntm + 1) + tm;
+        n_lo = o[0];
+        n_n = o[1] - n_lo;
+    };
+    auto advance = [&](int ck) {  // at the top of chunk ck: (n_lo, n_n) is the range of chunk ck + 2
+        p_lo = e_lo; p_n = e_n; p_pos = e_pos;
+        e_lo = f_lo; e_n = f_n; e_pos = f_pos;
+        f_lo = n_lo; f_n = n_n;
+        f_pos = ent_pos[f_lo + min(tid, max(f_n - 1, 0))];  // lanes past the bucket re-read its last entry
+        e_val = sv[e_lo + min(tid, max(e_n - 1, 0))];
+        offsets(ck + 3);
+    };
+    auto scatter = [&](int stage, int bm) {
+        const int n = e_n, lo = e_lo;
+        if (tid < n) put(stage, e_pos, e_val);  // (ranked by the caller)
+        for (int e = tid + W2_THREADS; e < n; e += W2_THREADS) put(stage, ranked(bm, ent_pos[lo + e]), sv[lo + e]);
+    };
+    auto setbits = [&](int bm) {
+        const int n = f_n, lo = f_lo;
+        if (tid < n) setbit(bm, f_pos);
+        for (int e = tid + W2_THREADS; e < n; e += W2_THREADS) setbit(bm, ent_pos[lo + e]);
+    };
+    auto unscatter = [&](int stage, int bm, bool l2) {
+        const int n = p_n, lo = p_lo;
+        if (tid < n) clear(stage, bm, p_pos, l2);
+        for (int e = tid + W2_THREADS; e < n; e += W2_THREADS) clear(stage, bm, ent_pos[lo + e], l2);
+        if (tid == 0) l2mask[stage] = 0u;
+    };
+
+    // bitmap of chunk c_begin + i: (i % 3); b0 / b1 / b2 = the bitmaps of the chunks p / e / f, rotated per chunk
+    int b0 = 2, b1 = 0, b2 = 1;
+    if (c_begin < c_end) {
+        // the pipeline is filled as if chunk c_begin - 1 had just run: e = c_begin, f = c_begin + 1
+        offsets(c_begin);
+        f_lo = n_lo; f_n = n_n;
+        f_pos = ent_pos[f_lo + min(tid, max(f_n - 1, 0))];
+        offsets(c_begin + 1);
+        advance(c_begin - 1);
+        rm_row(c_begin);
+        rm_use();
+        dma3(0, 0);
+        dma3(0, W2_PIECES / 2);
+        rm_row(min(c_begin + 1, c_end - 1));
+#pragma unroll
+        for (int st = 0; st < 2; ++st)
+#pragma unroll
+            for (int c = 0; c < W2_A_BYTES / 16 / W2_THREADS; ++c)
+                *(uint4*)(smem + st * W2_STAGE + (tid + c * W2_THREADS) * 16) = make_uint4(0, 0, 0, 0);
+        for (int c = tid; c < (W2S_LDS_BYTES - W2S_IX_OFF) / 16; c += W2_THREADS)
+            *(uint4*)(smem + W2S_IX_OFF + c * 16) = make_uint4(0, 0, 0, 0);
+        __syncthreads();
+        {  // the bits of chunk c_begin (its entries sit in e)
+            if (tid < e_n) setbit(b1, e_pos);
+            for (int e = tid + W2_THREADS; e < e_n; e += W2_THREADS) setbit(b1, ent_pos[e_lo + e]);
+        }
+        __syncthreads();
+        e_pos = ranked(b1, e_pos);
+        scatter(0, b1);
+        if (c_begin + 1 < c_end) setbits(b2);
+        dma_wait();
+        __syncthreads();
     }
+    for (int ck = c_begin; ck < c_end; ++ck) {
+        const int buf = (ck - c_begin) & 1;
+        char* cur = smem + buf * W2_STAGE;
+        const bool more = ck + 1 < c_end;
+        advance(ck);
+        { const int t = b0; b0 = b1; b1 = b2; b2 = t; }
+        e_pos = ranked(b1, e_pos);
+        rm_use();  // row pointer of chunk ck + 1 (its list entry was requested a chunk ago)
+        const uint32_t m2all = (uint32_t)__builtin_amdgcn_readfirstlane((int)l2mask[buf]);
+        Mfma96<T, W2_MI>::template slab_sparse<W2_M>(cur, ix_img + buf * (W2S_IX_BYTES / 4), smem_lds + buf * W2_STAGE + W2_A_BYTES,
+                                                     wm * 32 * W2_MI, wn * 96, lane,
+                                                     (m2all >> (wm * W2_MI)) & ((1u << W2_MI) - 1u), acc, [&](int kk) {
+            if (more && kk < 2) dma3(buf ^ 1, kk * (W2_PIECES / 2));
+            if (kk == 2) rm_row(min(ck + 2, c_end - 1));  // the row list entry of the chunk after next (an L2 hit by then)
+        });
+        if (do_dbe) {
+            Mfma96<T, W2_MI>::rowsum16(cur, wave * 16, lane, rs0);
+            if (wave + W2_WAVES < W2_M / 16) Mfma96<T, W2_MI>::rowsum16(cur, (wave + W2_WAVES) * 16, lane, rs1);
+        }
+        dma_wait();
+        __syncthreads();
+        if (more) {
+            unscatter(buf, b0, m2all != 0u);
+            scatter(buf ^ 1, b1);
+            if (ck + 2 < c_end) setbits(b2);
+        }
+        __syncthreads();
+    }
+
+    w2_epilogue(smem, acc, rs0, rs1, out, dbe_slab, which, split, f0, d0, wm, wn, wave, lane, H, D, nslots, dec_row_base, do_dbe);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1101,10 +1328,16 @@ static void launch_wgrad(wsae_ctx* ctx, const WgPlan& p, hipStream_t st, const f
         if constexpr (sizeof(T) == 2) {
             if (rm) {
                 const T* xsrc = ctx->xT_valid ? (const T*)ctx->xb : (const T*)x;
-                wgrad2_kernel<T, true><<<grid, W2_THREADS, 2 * W2_STAGE, st>>>(
-                    ctx->ent_pos, (const T*)ctx->ent_hid, (const T*)ctx->ent_dpre, ctx->ent_off, xsrc, (const T*)ctx->gb, B, ldT,
-                    ctx->H, ctx->D, p.nsplit, ntm, p.ntn, out, slab_stride, ctx->dbe_slab, ctx->xT_valid ? nullptr : rows,
-                    p.which0, p.nslots, p.dec_row_base);
+                if (ctx->wgrad_sparse)  // the TopK code on the 2:4 sparse MFMA (default; WSAE_WGRAD_SPARSE=0 keeps the dense form)
+                    wgrad2s_kernel<<<grid, W2_THREADS, W2S_LDS_BYTES, st>>>(
+                        ctx->ent_pos, (const bf16_t*)ctx->ent_hid, (const bf16_t*)ctx->ent_dpre, ctx->ent_off, (const bf16_t*)xsrc,
+                        (const bf16_t*)ctx->gb, B, ctx->H, ctx->D, p.nsplit, ntm, p.ntn, out, ctx->dbe_slab,
+                        ctx->xT_valid ? nullptr : rows, p.which0, p.nslots, p.dec_row_base);
+                else
+                    wgrad2_kernel<T, true><<<grid, W2_THREADS, 2 * W2_STAGE, st>>>(
+                        ctx->ent_pos, (const T*)ctx->ent_hid, (const T*)ctx->ent_dpre, ctx->ent_off, xsrc, (const T*)ctx->gb, B, ldT,
+                        ctx->H, ctx->D, p.nsplit, ntm, p.ntn, out, slab_stride, ctx->dbe_slab, ctx->xT_valid ? nullptr : rows,
+                        p.which0, p.nslots, p.dec_row_base);
                 done = true;
             }
         }
