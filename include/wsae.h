@@ -734,6 +734,43 @@ int wsae_sample_update(const float* vals, const int32_t* idx, int32_t k, int32_t
                        uint32_t seed, uint64_t* keys, float* svals, int32_t* seen, void* workspace, int64_t workspace_bytes,
                        void* stream);
 
+/* ---- label association: feature-by-class counts with lags -------------------------------------------
+ * Which feature detects which class of a per-frame label, at which activation threshold and how many frames early or
+ * late: integer counts per (feature, lag, class, value stratum) straight from a compact code vals / idx [n_rows, k]
+ * (1 <= k <= WSAE_LABEL_MAX_K) and labels int32 [n_rows], in one pass.  Ctx-free; the caller's stream, no allocation, no
+ * host synchronisation, no float atomics; argument errors are found on the host before any HIP call.
+ *
+ * Activity (the rule of wsae_profile_update): feature f is active on row r iff the row is not padding and some entry has
+ * idx == f, v > 0 and 0 <= f < hidden; an index repeated within a row counts once, with the value of its first active
+ * entry.  NaN is never active, +inf is.  seg int32 [n_rows] (nullable = one segment, no padding): a row with seg < 0 is
+ * padding.  Stratum (the rule of wsae_sample_update): edges fp32 [f_cols, n_strata - 1], ascending per feature of the
+ * window (1 <= n_strata <= WSAE_LABEL_MAX_STRATA; NULL allowed when n_strata == 1); the stratum of an active (r, f, v) is
+ * the number of f's edges that are <= v; a NaN edge is never <= v.
+ *
+ * Pairs.  The lags are lag_lo .. lag_hi with -1024 <= lag_lo <= lag_hi <= 1024 and L = lag_hi - lag_lo + 1 <=
+ * WSAE_LABEL_MAX_LAGS; lag 0 need not be among them.  (r, l) is a pair iff row r is not padding, 0 <= r + l < n_rows,
+ * seg[r + l] == seg[r] and 0 <= labels[r + l] < n_classes (1 <= n_classes <= WSAE_LABEL_MAX_CLASSES); its class is
+ * c = labels[r + l].  A label outside [0, n_classes) - -1 for "unlabelled" - drops the pair and nothing else.  Lags never
+ * cross an utterance: a call sees whole utterances.
+ *
+ * State (caller-owned device memory, zero-initialised): pair_rows int64 [L, n_classes] += 1 per pair, whatever the
+ * features do; cnt int32 [f_cols, L, n_classes, n_strata] += 1 per pair and per feature of the window
+ * (f_lo <= f < f_lo + f_cols) active on row r, at [f - f_lo][l - lag_lo][c][stratum]; offsets are computed in 64 bits.
+ * Every field is an integer sum: the state does not depend on the launch geometry, on the order of the calls or on the
+ * grouping of whole utterances into calls, and two states add.  0 <= n_rows <= 2^31 - 1 per call; n_rows == 0 returns
+ * WSAE_OK and touches nothing.  Workspace: wsae_label_workspace_bytes, 0 for valid arguments in this form (NULL is
+ * accepted then) and -1 for invalid ones; contents arbitrary on entry. */
+#define WSAE_LABEL_MAX_K 128
+#define WSAE_LABEL_MAX_CLASSES 1024
+#define WSAE_LABEL_MAX_LAGS 16
+#define WSAE_LABEL_MAX_STRATA 16
+int64_t wsae_label_workspace_bytes(int64_t n_rows, int32_t k, int32_t hidden, int32_t f_lo, int32_t f_cols,
+                                   int32_t n_classes, int32_t lag_lo, int32_t lag_hi, int32_t n_strata);
+int wsae_label_update(const float* vals, const int32_t* idx, int32_t k, int32_t hidden, const int32_t* seg,
+                      const int32_t* labels, int64_t n_rows, int32_t n_classes, int32_t lag_lo, int32_t lag_hi,
+                      int32_t f_lo, int32_t f_cols, const float* edges, int32_t n_strata, int32_t* cnt, int64_t* pair_rows,
+                      void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,7 @@
 // What the analysis kernels that walk a compact (values, indices) code share: the LDS pointer
-// types, the per-segment row bounds of a call, and the host-side checks on a code and its feature window.  Included by
-// wsae_groupstats.hip (pooling), wsae_runs.hip, wsae_sta.hip and, for the checks, wsae_coact.hip.
+// types, the per-segment row bounds of a call, the entry-per-thread walk (CodeArgs, pf_first_active) and the host-side
+// checks on a code and its feature window.  Included by wsae_groupstats.hip (pooling), wsae_runs.hip, wsae_sta.hip,
+// wsae_profile.hip and wsae_labels.hip (the entry-per-thread walk) and, for the checks, wsae_coact.hip.
 #pragma once
 #include <limits.h>
 
@@ -39,6 +40,53 @@ __global__ __launch_bounds__(256) void seg_bounds_kernel(const int32_t* __restri
 inline void seg_bounds(const int32_t* seg, int64_t n_rows, int n_seg, int32_t* first, int32_t* last, hipStream_t st) {
     seg_reset_kernel<<<ceil_div(n_seg, 256), 256, 0, st>>>(first, last, n_seg);
     seg_bounds_kernel<<<(int)ceil_div64(n_rows, 256), 256, 0, st>>>(seg, (int)n_rows, n_seg, first, last);
+}
+
+// ---- the entry-per-thread walk of wsae_profile.hip and wsae_labels.hip --------------------------------------------------
+struct CodeArgs {
+    const float* vals;
+    const int32_t* idx;
+    const int32_t* seg;  // nullable
+    int64_t n;           // n_rows * k
+    int k, f_lo, f_cols;
+};
+
+// One block pass over the entries base .. base + 255 of the flat code (thread = entry); called by all threads of the
+// block together.  true: the thread's entry is the first active entry of its (row, feature) on a non-padding row and the
+// feature lies in the window (which lies in [0, hidden): the host checked).  v, f, r: its value, feature and row;
+// row_head: the entry is column 0 of a non-padding row.
+__device__ __forceinline__ bool pf_first_active(const CodeArgs& a, int64_t base, int* s_idx, float& v, int& f, int64_t& r,
+                                                bool& row_head) {
+    const int t = threadIdx.x;
+    const int64_t e = base + t;
+    const int64_t r0 = base / a.k;  // (block-uniform)
+    const int j0 = (int)(base - r0 * a.k) + t;
+    r = r0 + j0 / a.k;
+    const int j = j0 % a.k;
+    v = 0.f;
+    f = -1;
+    bool live = false;
+    if (e < a.n) {
+        v = a.vals[e];
+        f = a.idx[e];
+        live = a.seg == nullptr || a.seg[r] >= 0;
+    }
+    row_head = live && j == 0;
+    const bool pos = v > 0.f;  // (NaN is not)
+    __syncthreads();           // the previous pass has been read
+    s_idx[t] = pos ? f : -1;
+    __syncthreads();
+    bool act = live && pos && f >= a.f_lo && f - a.f_lo < a.f_cols;
+    if (act) {
+        for (int d = 1; d <= j; ++d) {  // the row's earlier entries: entries e - 1 .. e - j
+            const int prev = t - d >= 0 ? s_idx[t - d] : (a.vals[e - d] > 0.f ? a.idx[e - d] : -1);
+            if (prev == f) {
+                act = false;
+                break;
+            }
+        }
+    }
+    return act;
 }
 
 // ---- host side: the checks every entry point makes on a code and its feature window ------------------------------------

@@ -17,9 +17,10 @@
 // an entry whose key is not below the last key of its list as the list stands when the call begins can never enter
 // (lists only tighten), so its `seen` is counted and it goes no further.
 //
-// Both walk the code the same way (pf_first_active): an index repeated within a row counts once, with the value of its
-// first active entry, which needs the row's earlier entries only - they are the thread's left neighbours in the block's
-// LDS, or, for a row that began in the previous 256 entries, a few global loads.
+// Both walk the code the same way (pf_first_active in wsae_codewalk.h, shared with wsae_labels.hip): an index repeated
+// within a row counts once, with the value of its first active entry, which needs the row's earlier entries only - they
+// are the thread's left neighbours in the block's LDS, or, for a row that began in the previous 256 entries, a few
+// global loads.
 #include <limits.h>
 
 #include "wsae_codewalk.h"
@@ -32,52 +33,6 @@ constexpr int PF_BINS = WSAE_PROFILE_BINS;
 constexpr int PF_LDS_COLS = 4096;   // the widest window whose fires and sum_q a block keeps in LDS (48 KB)
 constexpr int PF_LDS_BLOCKS = 768;  // ... three such blocks per CU; a block ends with at most 2 f_cols global atomics
 constexpr unsigned long long SM_EMPTY = ~0ull;  // an unused slot of a list: no key reaches it (ordinals stay below 2^31)
-
-struct CodeArgs {
-    const float* vals;
-    const int32_t* idx;
-    const int32_t* seg;  // nullable
-    int64_t n;           // n_rows * k
-    int k, f_lo, f_cols;
-};
-
-// One block pass over the entries base .. base + 255 of the flat code (thread = entry); called by all threads of the
-// block together.  true: the thread's entry is the first active entry of its (row, feature) on a non-padding row and the
-// feature lies in the window (which lies in [0, hidden): the host checked).  v, f, r: its value, feature and row;
-// row_head: the entry is column 0 of a non-padding row.
-__device__ __forceinline__ bool pf_first_active(const CodeArgs& a, int64_t base, int* s_idx, float& v, int& f, int64_t& r,
-                                                bool& row_head) {
-    const int t = threadIdx.x;
-    const int64_t e = base + t;
-    const int64_t r0 = base / a.k;  // (block-uniform)
-    const int j0 = (int)(base - r0 * a.k) + t;
-    r = r0 + j0 / a.k;
-    const int j = j0 % a.k;
-    v = 0.f;
-    f = -1;
-    bool live = false;
-    if (e < a.n) {
-        v = a.vals[e];
-        f = a.idx[e];
-        live = a.seg == nullptr || a.seg[r] >= 0;
-    }
-    row_head = live && j == 0;
-    const bool pos = v > 0.f;  // (NaN is not)
-    __syncthreads();           // the previous pass has been read
-    s_idx[t] = pos ? f : -1;
-    __syncthreads();
-    bool act = live && pos && f >= a.f_lo && f - a.f_lo < a.f_cols;
-    if (act) {
-        for (int d = 1; d <= j; ++d) {  // the row's earlier entries: entries e - 1 .. e - j
-            const int prev = t - d >= 0 ? s_idx[t - d] : (a.vals[e - d] > 0.f ? a.idx[e - d] : -1);
-            if (prev == f) {
-                act = false;
-                break;
-            }
-        }
-    }
-    return act;
-}
 
 // ---- the value histogram and moments ------------------------------------------------------------------------------------
 struct ProfileOut {

@@ -1,8 +1,10 @@
 """Feature analysis right after the SAE path: per-feature top activations kept on the
 device, the comparison of two dictionaries by their decoder (or encoder) directions, co-activation statistics of
 their codes, effect sizes of the features between two groups of utterances, the temporal run statistics of the
-features (run lengths, gaps, event lists), feature-triggered averages of a per-frame signal, and activation profiles
-(per-feature value histograms and uniform samples per value stratum).  Mirrors the names of the reference's ``whisper_sae.analysis.feature_viz``
+features (run lengths, gaps, event lists), feature-triggered averages of a per-frame signal, activation profiles
+(per-feature value histograms and uniform samples per value stratum), and label association (feature-by-class counts per
+value stratum and lag against a per-frame label: precision, recall, F1, phi, mutual information and AUROC at the best
+threshold and lag).  Mirrors the names of the reference's ``whisper_sae.analysis.feature_viz``
 that sit on that path."""
 
 from .coactivation import (CoactivationNeighbors, CoactivationTracker, collect_coactivation,
@@ -11,6 +13,8 @@ from .dictionary import NearestFeatures, compare_dictionaries, duplicate_feature
 from .feature_viz import FeatureActivation, TopKTracker, collect_top_activations
 from .group_stats import (GroupEffects, SegmentPooler, bootstrap_weights, collect_pooled, group_effect_sizes,
                           top_group_features)
+from .labels import (BestLabels, LabelAssociation, LabelScores, automated_labels, best_labels, collect_label_association,
+                     top_label_features)
 from .profile import (ActivationProfile, ActivationSampler, DensityHistogram, ProfileSummary, SampledActivations,
                       collect_activation_profile, collect_activation_samples, top_profile_features)
 from .temporal import FeatureEvents, RunSummary, RunTracker, collect_runs, summarize_runs, top_temporal_features
@@ -24,4 +28,5 @@ __all__ = ["FeatureActivation", "TopKTracker", "collect_top_activations", "Neare
            "collect_runs", "summarize_runs", "top_temporal_features", "TriggeredAverageTracker", "collect_triggered_averages",
            "mel_frames", "as_spectrogram", "top_template_features", "ActivationProfile", "ActivationSampler", "DensityHistogram",
            "ProfileSummary", "SampledActivations", "collect_activation_profile", "collect_activation_samples",
-           "top_profile_features"]
+           "top_profile_features", "BestLabels", "LabelAssociation", "LabelScores", "automated_labels", "best_labels",
+           "collect_label_association", "top_label_features"]
