@@ -771,6 +771,64 @@ int wsae_label_update(const float* vals, const int32_t* idx, int32_t k, int32_t 
                       int32_t f_lo, int32_t f_cols, const float* edges, int32_t n_strata, int32_t* cnt, int64_t* pair_rows,
                       void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- sparse linear probes: softmax regression on the compact code -----------------------------------
+ * How well does a SET of features predict a per-frame label?  The two sparse products of one iteration of a softmax
+ * regression over a compact code vals / idx [n_rows, k] (1 <= k <= WSAE_PROBE_MAX_K); the dense [n_rows, hidden] code
+ * never exists.  Ctx-free; the caller's stream, no allocation, no host synchronisation, no float atomics; argument
+ * errors are found on the host before any HIP call; n_rows == 0 returns WSAE_OK and touches nothing; every
+ * *_workspace_bytes returns -1 for invalid arguments; workspace contents are arbitrary on entry.
+ *
+ * Activity is the rule of wsae_profile_update (above): seg[r] >= 0 (NULL: one segment, no padding), some entry with
+ * idx == f, v > 0 and 0 <= f < hidden; a repeated index counts once, with the value of its first active entry; NaN is
+ * never active.  Columns: col_of int32 [hidden] maps a feature to its probe column in [0, n_cols), -1 = not in the probe;
+ * NULL = the identity, and then n_cols == hidden.  A value outside [-1, n_cols) and two features on one column are the
+ * caller's errors and are not detected.
+ *
+ * wsae_probe_plan transposes the code: one entry per active (row, feature) with a column, grouped by column and in
+ * ascending row within a column (a stable counting sort).  col_ptr int64 [n_cols + 1], t_row int32 [cap], t_val fp32
+ * [cap], nnz int64 [1].  col_ptr and nnz always describe ALL entries; slots from cap on are not written, so a caller who
+ * finds nnz > cap grows the buffers and calls again.  The result depends on the code, seg and col_of only.
+ *
+ * wsae_probe_forward.  The label of row r is labels[r + lag] (-1024 <= lag <= 1024); it is valid iff r is not padding,
+ * 0 <= r + lag < n_rows, seg[r + lag] == seg[r] and the label lies in [0, n_classes).  Otherwise the row is dropped: its
+ * err row is exact zeros, its row_loss 0, it counts nowhere.  On a used row with label y
+ *   logit[c] = bias[c] + sum_j v_j W[col_j][c]   over the row's first-active entries with a column, in ascending entry
+ *              position; every step is an fp32 multiply and then an fp32 add (NOT fused), W fp32 [n_cols, ldw];
+ *   m = max logit, e_c = expf(logit[c] - m), s = sum e_c, loss = w_y ((logf(s) + m) - logit[y]),
+ *   err[c] = w_y (e_c / s - [c == y]),   w = class_weight fp32 [n_classes] (NULL: 1).
+ * The maximum and the sum over classes are taken as 64 partials (partial l over the classes l, l + 64, ... ascending,
+ * from -inf / 0) combined by a butterfly at distances 32, 16, 8, 4, 2, 1; what is written for a row depends on that row
+ * alone.  Outputs, each nullable one skipped when NULL: err fp32 [n_rows, lde] (nullable; lde >= n_classes, columns from
+ * n_classes on are never written); row_loss fp32 [n_rows] (nullable); n_used, n_correct (argmax == y, ties to the lowest
+ * class), loss_q int64 [1] += llrint(min(loss, 1024) 2^20); confusion int64 [n_classes, n_classes] (nullable) += 1 at
+ * [y][argmax].  The four are integer sums on caller-owned state: identical for any batching of whole utterances and any
+ * call order, and two shards add.
+ *
+ * wsae_probe_backward: gW fp64 [n_cols, n_classes] and gb fp64 [n_classes] accumulate from the stored value.  With the
+ * entries i = 0 .. n_p - 1 of column p (clipped to cap), partial_q[c] is ONE chain of fp64 additions, started at 0, of
+ * double(t_val[i]) double(err[t_row[i]][c]) over i = q CHUNK .. min((q + 1) CHUNK, n_p) - 1 in order (CHUNK =
+ * WSAE_PROBE_CHUNK; the product is exact), and gW[p][c] = ((stored + partial_0) + partial_1) + ...; a column without
+ * entries is not touched.  gb[c] the same over chunks of CHUNK consecutive rows of the call with terms double(err[r][c]).
+ * A sequential loop reproduces every bit; the result depends neither on the launch geometry nor on lde. */
+#define WSAE_PROBE_MAX_K 128
+#define WSAE_PROBE_MAX_CLASSES 1024
+#define WSAE_PROBE_CHUNK 2048
+int64_t wsae_probe_plan_workspace_bytes(int64_t n_rows, int32_t k, int32_t hidden, int32_t n_cols);
+int wsae_probe_plan(const float* vals, const int32_t* idx, int32_t k, int32_t hidden, const int32_t* seg, int64_t n_rows,
+                    const int32_t* col_of, int32_t n_cols, int64_t* col_ptr, int32_t* t_row, float* t_val, int64_t cap,
+                    int64_t* nnz, void* workspace, int64_t workspace_bytes, void* stream);
+int64_t wsae_probe_forward_workspace_bytes(int64_t n_rows, int32_t k, int32_t hidden, int32_t n_cols, int32_t n_classes,
+                                           int32_t lag);
+int wsae_probe_forward(const float* vals, const int32_t* idx, int32_t k, int32_t hidden, const int32_t* seg,
+                       const int32_t* labels, int64_t n_rows, int32_t lag, int32_t n_classes, const int32_t* col_of,
+                       int32_t n_cols, const float* W, int64_t ldw, const float* bias, const float* class_weight, float* err,
+                       int64_t lde, float* row_loss, int64_t* n_used, int64_t* n_correct, int64_t* loss_q, int64_t* confusion,
+                       void* workspace, int64_t workspace_bytes, void* stream);
+int64_t wsae_probe_backward_workspace_bytes(int64_t n_rows, int32_t n_cols, int32_t n_classes, int64_t cap);
+int wsae_probe_backward(const int64_t* col_ptr, const int32_t* t_row, const float* t_val, int64_t cap, int32_t n_cols,
+                        const float* err, int64_t lde, int32_t n_classes, int64_t n_rows, double* gW, double* gb,
+                        void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,7 +4,8 @@ their codes, effect sizes of the features between two groups of utterances, the 
 features (run lengths, gaps, event lists), feature-triggered averages of a per-frame signal, activation profiles
 (per-feature value histograms and uniform samples per value stratum), and label association (feature-by-class counts per
 value stratum and lag against a per-frame label: precision, recall, F1, phi, mutual information and AUROC at the best
-threshold and lag).  Mirrors the names of the reference's ``whisper_sae.analysis.feature_viz``
+threshold and lag), and sparse linear probes (softmax regression of a label on the compact code over all or a subset of
+the features, and the k-sparse probing curve).  Mirrors the names of the reference's ``whisper_sae.analysis.feature_viz``
 that sit on that path."""
 
 from .coactivation import (CoactivationNeighbors, CoactivationTracker, collect_coactivation,
@@ -15,6 +16,8 @@ from .group_stats import (GroupEffects, SegmentPooler, bootstrap_weights, collec
                           top_group_features)
 from .labels import (BestLabels, LabelAssociation, LabelScores, automated_labels, best_labels, collect_label_association,
                      top_label_features)
+from .probe import (ProbeCurve, ProbeData, ProbeFit, ProbeReport, SparseProbe, collect_probe_data, sparse_probe_curve,
+                    utterance_split)
 from .profile import (ActivationProfile, ActivationSampler, DensityHistogram, ProfileSummary, SampledActivations,
                       collect_activation_profile, collect_activation_samples, top_profile_features)
 from .temporal import FeatureEvents, RunSummary, RunTracker, collect_runs, summarize_runs, top_temporal_features
@@ -29,4 +32,5 @@ __all__ = ["FeatureActivation", "TopKTracker", "collect_top_activations", "Neare
            "mel_frames", "as_spectrogram", "top_template_features", "ActivationProfile", "ActivationSampler", "DensityHistogram",
            "ProfileSummary", "SampledActivations", "collect_activation_profile", "collect_activation_samples",
            "top_profile_features", "BestLabels", "LabelAssociation", "LabelScores", "automated_labels", "best_labels",
-           "collect_label_association", "top_label_features"]
+           "collect_label_association", "top_label_features", "ProbeCurve", "ProbeData", "ProbeFit", "ProbeReport", "SparseProbe",
+           "collect_probe_data", "sparse_probe_curve", "utterance_split"]
