@@ -829,6 +829,53 @@ int wsae_probe_backward(const int64_t* col_ptr, const int32_t* t_row, const floa
                         const float* err, int64_t lde, int32_t n_classes, int64_t n_rows, double* gW, double* gb,
                         void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- sparse ridge regression: the code's Gram matrix and the linear forward --------------------------
+ * How well does a feature, or a set of features, track a CONTINUOUS per-frame quantity?  The sufficient statistics of a
+ * linear regression on a compact code vals / idx [n_rows, k] (1 <= k <= WSAE_PROBE_MAX_K) are its Gram matrix G = X^T X and
+ * the cross moment M = X^T Y; the dense [n_rows, hidden] code X never exists.  M is wsae_probe_backward with the target
+ * rows in the place of err.  Ctx-free; the caller's stream, no allocation, no host synchronisation, no float atomics;
+ * argument errors are found on the host before any HIP call; n_rows == 0 returns WSAE_OK and touches nothing; every
+ * *_workspace_bytes returns -1 for invalid arguments; workspace contents are arbitrary on entry.  Activity, padding
+ * (seg[r] < 0; NULL: none) and col_of / n_cols are those of wsae_probe_plan (above).
+ *
+ * wsae_gram_update.  col_ptr / t_row / t_val / cap: the plan wsae_probe_plan made of this very code, seg and col_of.  With
+ * u_c(r) the value with which column c is active on row r, and the entries i = 0 .. n_p - 1 of column p (clipped to cap),
+ * partial_q[c] is ONE chain of fp64 additions, started at 0, of double(t_val[i]) double(u_c(t_row[i])) over
+ * i = q CHUNK .. min((q + 1) CHUNK, n_p) - 1 in order (CHUNK = WSAE_PROBE_CHUNK), over those i only on whose row c is
+ * active; the product of two fp32 values is exact in fp64.  For the rows p of the window p_lo <= p < p_lo + p_rows
+ * (inside [0, n_cols)) and c >= p:  G[p - p_lo][c] = ((stored + partial_0) + partial_1) + ...;  G fp64 [p_rows, ldg],
+ * ldg >= n_cols <= WSAE_GRAM_MAX_COLS.  Only the upper triangle is produced: cells with c < p and columns from n_cols on
+ * are never written, and a column p without entries touches nothing.  On the diagonal u_p(r) is the very t_val[i].  An
+ * entry whose t_row lies outside [0, n_rows) or on a padding row adds nothing.  A sequential loop reproduces every bit;
+ * the result depends on the code, seg, col_of, the stored G and the sequence of calls - not on the launch geometry, ldg,
+ * the split into row windows or the workspace.  Workspace (8-byte aligned): wsae_gram_workspace_bytes - 8 bytes per entry
+ * of the code (n_rows k): every call first writes the column and the value of every entry there, once per row.
+ *
+ * wsae_regress_forward.  Y fp32 [n_rows, ldy] (nullable), 1 <= n_targets <= WSAE_PROBE_MAX_CLASSES; the target of row r is
+ * Y[r + lag] (-1024 <= lag <= 1024).  Row r is USED iff it is not padding, 0 <= r + lag < n_rows, seg[r + lag] == seg[r]
+ * and all n_targets values of Y[r + lag] are finite.  W fp64 [n_cols, ldw], bias fp64 [n_targets]:
+ *   yhat[c] = bias[c], then + double(v_j) W[col_j][c] over the row's first-active entries with a column, in ascending
+ *             entry position; every step is an fp64 multiply and then an fp64 add (NOT fused).
+ * pred fp32 [n_rows, ldp] (nullable; columns from n_targets on are never written) = float(yhat) on every non-padding row,
+ * used or not, and exact zeros on a padding row.  With Y: n_used int64 [1] += the used rows (an integer sum); stats fp64
+ * [5, n_targets] accumulates sum y, sum y^2, sum yhat, sum yhat^2, sum (y - yhat)^2 over the used rows, yhat in fp64 and
+ * every square an fp64 multiply: per cell and chunk of CHUNK consecutive rows of the call ONE chain of fp64 additions
+ * from 0 in row order (unused rows add nothing), and stats = ((stored + partial_0) + partial_1) + ...  With Y == NULL only
+ * pred is written (and is required).  Workspace (8-byte aligned): wsae_regress_forward_workspace_bytes - 40 bytes per
+ * chunk and target; not needed when Y == NULL. */
+#define WSAE_GRAM_MAX_COLS 8192
+int64_t wsae_gram_workspace_bytes(int64_t n_rows, int32_t k, int32_t hidden, int32_t n_cols, int32_t p_rows, int64_t cap);
+int wsae_gram_update(const float* vals, const int32_t* idx, int32_t k, int32_t hidden, const int32_t* seg, int64_t n_rows,
+                     const int32_t* col_of, int32_t n_cols, const int64_t* col_ptr, const int32_t* t_row, const float* t_val,
+                     int64_t cap, int32_t p_lo, int32_t p_rows, double* G, int64_t ldg, void* workspace,
+                     int64_t workspace_bytes, void* stream);
+int64_t wsae_regress_forward_workspace_bytes(int64_t n_rows, int32_t k, int32_t hidden, int32_t n_cols, int32_t n_targets,
+                                             int32_t lag);
+int wsae_regress_forward(const float* vals, const int32_t* idx, int32_t k, int32_t hidden, const int32_t* seg, const float* Y,
+                         int64_t ldy, int64_t n_rows, int32_t lag, int32_t n_targets, const int32_t* col_of, int32_t n_cols,
+                         const double* W, int64_t ldw, const double* bias, float* pred, int64_t ldp, int64_t* n_used,
+                         double* stats, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

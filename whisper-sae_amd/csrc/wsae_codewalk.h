@@ -1,7 +1,8 @@
 // What the analysis kernels that walk a compact (values, indices) code share: the LDS pointer
 // types, the per-segment row bounds of a call, the entry-per-thread walk (CodeArgs, pf_first_active) and the host-side
 // checks on a code and its feature window.  Included by wsae_groupstats.hip (pooling), wsae_runs.hip, wsae_sta.hip,
-// wsae_profile.hip and wsae_labels.hip (the entry-per-thread walk) and, for the checks, wsae_coact.hip.
+// wsae_profile.hip and wsae_labels.hip (the entry-per-thread walk), wsae_probe.hip and wsae_regress.hip (the wave-per-row
+// front end) and, for the checks, wsae_coact.hip.
 #pragma once
 #include <limits.h>
 
@@ -16,6 +17,7 @@ typedef __attribute__((address_space(3))) volatile float lds_f32;
 typedef __attribute__((address_space(3))) volatile int lds_i32;
 typedef __attribute__((address_space(3))) volatile uint8_t lds_u8;
 typedef __attribute__((address_space(3))) volatile unsigned long long lds_u64;
+typedef __attribute__((address_space(3))) volatile double lds_f64;
 
 __global__ __launch_bounds__(256) void seg_reset_kernel(int32_t* __restrict__ first, int32_t* __restrict__ last, int n_seg) {
     const int s = blockIdx.x * 256 + threadIdx.x;
@@ -87,6 +89,43 @@ __device__ __forceinline__ bool pf_first_active(const CodeArgs& a, int64_t base,
         }
     }
     return act;
+}
+
+// ---- the wave-per-row front end of wsae_probe.hip and wsae_regress.hip: one lane per entry, two for k > 64 ----------------
+// The entries lane and lane + 64 of one row.  col0 / col1: the probe column where the entry is the first active entry of
+// its feature on the row and the feature has a column, else -1.  Called by the whole wave; the row is not padding.
+__device__ __forceinline__ void probe_row_columns(float v0, int f0, float v1, int f1, int k, int hidden,
+                                                  const int32_t* __restrict__ col_of, int lane, int& col0, int& col1) {
+    const int p0 = v0 > 0.f ? f0 : -1;  // (NaN is not; an absent entry carries v = 0)
+    const int p1 = v1 > 0.f ? f1 : -1;
+    bool dup0 = false, dup1 = false;
+    const int k0 = k < 64 ? k : 64;
+    for (int d = 0; d < k0; ++d) {  // (wave-uniform)
+        const int g = __builtin_amdgcn_readlane(p0, d);
+        dup0 |= d < lane && g == p0;
+        dup1 |= g == p1;
+    }
+    for (int d = 64; d < k; ++d) {
+        const int g = __builtin_amdgcn_readlane(p1, d - 64);
+        dup1 |= d - 64 < lane && g == p1;
+    }
+    col0 = -1;
+    col1 = -1;
+    if (p0 >= 0 && p0 < hidden && !dup0) col0 = col_of ? col_of[p0] : p0;
+    if (p1 >= 0 && p1 < hidden && !dup1) col1 = col_of ? col_of[p1] : p1;
+}
+
+__device__ __forceinline__ void probe_load_row(const float* __restrict__ vals, const int32_t* __restrict__ idx, int k, int64_t r,
+                                               int lane, float& v0, int& f0, float& v1, int& f1) {
+    v0 = 0.f, v1 = 0.f, f0 = -1, f1 = -1;
+    if (lane < k) {
+        v0 = vals[r * k + lane];
+        f0 = idx[r * k + lane];
+    }
+    if (lane + 64 < k) {
+        v1 = vals[r * k + lane + 64];
+        f1 = idx[r * k + lane + 64];
+    }
 }
 
 // ---- host side: the checks every entry point makes on a code and its feature window ------------------------------------

@@ -45,41 +45,7 @@ constexpr int PB_CHUNK = WSAE_PROBE_CHUNK;
 
 static_assert((PB_CHUNK & (PB_CHUNK - 1)) == 0 && PB_CHUNK >= 64, "WSAE_PROBE_CHUNK must be a power of two >= 64");
 
-// The entries lane and lane + 64 of one row.  col0 / col1: the probe column where the entry is the first active entry of
-// its feature on the row and the feature has a column, else -1.  Called by the whole wave; the row is not padding.
-__device__ __forceinline__ void probe_row_columns(float v0, int f0, float v1, int f1, int k, int hidden,
-                                                  const int32_t* __restrict__ col_of, int lane, int& col0, int& col1) {
-    const int p0 = v0 > 0.f ? f0 : -1;  // (NaN is not; an absent entry carries v = 0)
-    const int p1 = v1 > 0.f ? f1 : -1;
-    bool dup0 = false, dup1 = false;
-    const int k0 = k < 64 ? k : 64;
-    for (int d = 0; d < k0; ++d) {  // (wave-uniform)
-        const int g = __builtin_amdgcn_readlane(p0, d);
-        dup0 |= d < lane && g == p0;
-        dup1 |= g == p1;
-    }
-    for (int d = 64; d < k; ++d) {
-        const int g = __builtin_amdgcn_readlane(p1, d - 64);
-        dup1 |= d - 64 < lane && g == p1;
-    }
-    col0 = -1;
-    col1 = -1;
-    if (p0 >= 0 && p0 < hidden && !dup0) col0 = col_of ? col_of[p0] : p0;
-    if (p1 >= 0 && p1 < hidden && !dup1) col1 = col_of ? col_of[p1] : p1;
-}
-
-__device__ __forceinline__ void probe_load_row(const float* __restrict__ vals, const int32_t* __restrict__ idx, int k, int64_t r,
-                                               int lane, float& v0, int& f0, float& v1, int& f1) {
-    v0 = 0.f, v1 = 0.f, f0 = -1, f1 = -1;
-    if (lane < k) {
-        v0 = vals[r * k + lane];
-        f0 = idx[r * k + lane];
-    }
-    if (lane + 64 < k) {
-        v1 = vals[r * k + lane + 64];
-        f1 = idx[r * k + lane + 64];
-    }
-}
+// (probe_load_row and probe_row_columns, the row front end shared with wsae_regress.hip, are in wsae_codewalk.h)
 
 // ---- the plan ---------------------------------------------------------------------------------------------------------------
 template <bool SCATTER>

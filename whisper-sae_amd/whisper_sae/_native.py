@@ -27,6 +27,7 @@ STA_MAX_K, STA_MAX_LAGS, STA_MAX_CH = 128, 64, 4096
 PROFILE_MAX_K, PROFILE_BINS, SAMPLE_MAX_STRATA, SAMPLE_MAX_KEEP = 128, 192, 16, 64  # wsae_profile_update / wsae_sample_update
 LABEL_MAX_K, LABEL_MAX_CLASSES, LABEL_MAX_LAGS, LABEL_MAX_STRATA = 128, 1024, 16, 16  # wsae_label_update
 PROBE_MAX_K, PROBE_MAX_CLASSES, PROBE_CHUNK = 128, 1024, 2048  # wsae_probe_plan / wsae_probe_forward / wsae_probe_backward
+GRAM_MAX_COLS = 8192  # wsae_gram_update
 BTK_STATE_WORDS = 8  # wsae_batch_topk_state: threshold, beta, last_t (f32), saturated_rows, kept, 3 reserved (i32)
 
 
@@ -144,6 +145,11 @@ SIGNATURES = {
                                      _p, _p, _p, _i64, _p]),
     "wsae_probe_backward_workspace_bytes": (_i64, [_i64, _i32, _i32, _i64]),
     "wsae_probe_backward": (C.c_int, [_p, _p, _p, _i64, _i32, _p, _i64, _i32, _i64, _p, _p, _p, _i64, _p]),
+    "wsae_gram_workspace_bytes": (_i64, [_i64, _i32, _i32, _i32, _i32, _i64]),
+    "wsae_gram_update": (C.c_int, [_p, _p, _i32, _i32, _p, _i64, _p, _i32, _p, _p, _p, _i64, _i32, _i32, _p, _i64, _p, _i64, _p]),
+    "wsae_regress_forward_workspace_bytes": (_i64, [_i64, _i32, _i32, _i32, _i32, _i32]),
+    "wsae_regress_forward": (C.c_int, [_p, _p, _i32, _i32, _p, _p, _i64, _i64, _i32, _i32, _p, _i32, _p, _i64, _p, _p, _i64, _p, _p,
+                                       _p, _i64, _p]),
     "wsae_relu_needs_hidden":(C.c_int, [_p, _i32]),
     "wsae_relu_forward": (C.c_int, [_p, _p, _p, _i32, _p, _i32, _f32, _p, _p, _p, _p, _p]),
     "wsae_relu_backward": (C.c_int, [_p, _p, _p, _i32, _p, _i32, _f32, _p, _p, _p, _p]),

@@ -5,7 +5,8 @@ features (run lengths, gaps, event lists), feature-triggered averages of a per-f
 (per-feature value histograms and uniform samples per value stratum), and label association (feature-by-class counts per
 value stratum and lag against a per-frame label: precision, recall, F1, phi, mutual information and AUROC at the best
 threshold and lag), and sparse linear probes (softmax regression of a label on the compact code over all or a subset of
-the features, and the k-sparse probing curve).  Mirrors the names of the reference's ``whisper_sae.analysis.feature_viz``
+the features, and the k-sparse probing curve), and sparse ridge regression (the Gram matrix of the code and the target
+moments in one streaming pass, then ridge fits of any feature subset as host-side solves).  Mirrors the names of the reference's ``whisper_sae.analysis.feature_viz``
 that sit on that path."""
 
 from .coactivation import (CoactivationNeighbors, CoactivationTracker, collect_coactivation,
@@ -20,6 +21,8 @@ from .probe import (ProbeCurve, ProbeData, ProbeFit, ProbeReport, SparseProbe, c
                     utterance_split)
 from .profile import (ActivationProfile, ActivationSampler, DensityHistogram, ProfileSummary, SampledActivations,
                       collect_activation_profile, collect_activation_samples, top_profile_features)
+from .regression import (RegressionCurve, RegressionFit, RegressionReport, SparseRegression, collect_regression,
+                         regression_curve, ridge_from_statistics, top_correlated_features)
 from .temporal import FeatureEvents, RunSummary, RunTracker, collect_runs, summarize_runs, top_temporal_features
 from .triggered import (TriggeredAverageTracker, as_spectrogram, collect_triggered_averages, mel_frames,
                         top_template_features)
@@ -33,4 +36,5 @@ __all__ = ["FeatureActivation", "TopKTracker", "collect_top_activations", "Neare
            "ProfileSummary", "SampledActivations", "collect_activation_profile", "collect_activation_samples",
            "top_profile_features", "BestLabels", "LabelAssociation", "LabelScores", "automated_labels", "best_labels",
            "collect_label_association", "top_label_features", "ProbeCurve", "ProbeData", "ProbeFit", "ProbeReport", "SparseProbe",
-           "collect_probe_data", "sparse_probe_curve", "utterance_split"]
+           "collect_probe_data", "sparse_probe_curve", "utterance_split", "RegressionCurve", "RegressionFit", "RegressionReport",
+           "SparseRegression", "collect_regression", "regression_curve", "ridge_from_statistics", "top_correlated_features"]
