@@ -371,3 +371,22 @@ def planted_case():
     idx[on, 0] = np.array(planted)[state[on] - 1]
     vals[on, 0] = rng.uniform(0.5, 2.0, int(on.sum())).astype(np.float32)
     return (vals, idx), state.astype(np.int64)[None], planted
+
+
+DENSE_UTT, DENSE_T, DENSE_K, DENSE_HIDDEN = 8, 256, 8, 1024
+DENSE_FEATURES = (700, 3, 1000, 17, 512, 41, 64, 35)
+
+
+def dense_subset_case():
+    """(code [n_utt, T, k], col_of, P): every one of the 2048 rows holds the eight features of ``DENSE_FEATURES``, in an
+    order of its own and with positive values, so that a tracker over that subset of a 1024-feature dictionary finds all
+    16384 entries where its first guess - the subset's share of the dictionary, ``1024 + 2 * 16384 * 8 // 1024 = 1280`` -
+    expects few: the plan is transposed twice."""
+    rng = np.random.default_rng(2800)
+    rows = DENSE_UTT * DENSE_T
+    idx = np.array(DENSE_FEATURES, np.int32)[np.argsort(rng.random((rows, DENSE_K)), axis=1)]
+    vals = rng.uniform(0.1, 2.0, (rows, DENSE_K)).astype(np.float32)
+    col_of = np.full(DENSE_HIDDEN, -1, np.int32)
+    col_of[list(DENSE_FEATURES)] = np.arange(DENSE_K)
+    shape = (DENSE_UTT, DENSE_T, DENSE_K)
+    return (vals.reshape(shape), idx.reshape(shape)), col_of, DENSE_K

@@ -1,7 +1,8 @@
 """The forms in which the analysis trackers take a code, on the MI355X: one small batch given as ``[n_utt, T, k]`` with a
 ``frame_mask``, as flat rows whose padding is segment -1, and as flat rows with a flat ``frame_mask`` must leave the same
 state, bit for bit (the float sums included: the order of the additions is fixed).  Three frames are padding: one
-inside an utterance, where it splits a run, the last frame of an utterance and the first frame of another."""
+inside an utterance, where it splits a run, the last frame of an utterance and the first frame of another.  And the
+files of the trackers that keep their tensors in a ``_state`` dict: their keys, and that they load into the same state."""
 
 from __future__ import annotations
 
@@ -9,7 +10,8 @@ import numpy as np
 import pytest
 import torch
 
-from whisper_sae.analysis import CoactivationTracker, RunTracker, SegmentPooler, TriggeredAverageTracker
+from whisper_sae.analysis import (ActivationProfile, ActivationSampler, CoactivationTracker, LabelAssociation, RunTracker,
+                                  SegmentPooler, TriggeredAverageTracker)
 
 pytestmark = pytest.mark.gpu
 
@@ -109,3 +111,53 @@ def test_coactivation_tracker(batch):
     tb.update(batch["code2"], row_mask=batch["mask2"])
     same_fields((ta, tb), ("counts", "fire_a"))
     assert ta.rows == tb.rows == N_UTT * T - len(MASKED) == int(ta.fire_a[ALWAYS])
+
+
+# ---- saved files: the keys a file has had since the tracker was added (a file written then must load now, and back) -------------
+EDGES = torch.tensor([[0.5, 1.0]]).repeat(HIDDEN, 1)
+SAVED = {
+    "label_association": (lambda: LabelAssociation(HIDDEN, 3, EDGES, lags=(-1, 1), device=DEV),
+                          ("hidden", "n_classes", "lags", "f_window", "edges", "form", "submitted", "state"),
+                          ("cnt", "pair_rows")),
+    "activation_profile": (lambda: ActivationProfile(HIDDEN, device=DEV), ("hidden", "f_window", "submitted", "state"),
+                           ("fires", "hist", "max_bits", "min_bits", "over", "sum_q", "total_rows")),
+    "activation_sampler": (lambda: ActivationSampler(HIDDEN, EDGES, keep=4, seed=3, device=DEV),
+                           ("hidden", "f_window", "keep", "seed", "ordinal_base", "next", "records", "edges", "state"),
+                           ("keys", "svals", "seen")),
+    "run_tracker": (lambda: RunTracker(HIDDEN, max_events=64, device=DEV),
+                    ("hidden", "f_window", "gaps", "max_events", "min_event_len", "next", "form", "submitted", "state"),
+                    ("frames", "runs", "dur_max", "dur_sq", "dur_hist", "gap_hist", "total_rows", "ev_int", "ev_flt", "ev_count")),
+    "run_tracker_bare": (lambda: RunTracker(HIDDEN, gaps=False, device=DEV),  # (no gap histogram, no events: None in the file)
+                         ("hidden", "f_window", "gaps", "max_events", "min_event_len", "next", "form", "submitted", "state"),
+                         ("frames", "runs", "dur_max", "dur_sq", "dur_hist", "gap_hist", "total_rows", "ev_int", "ev_flt",
+                          "ev_count")),
+    "triggered_average": (lambda: TriggeredAverageTracker(HIDDEN, CHANNELS, lags=LAGS, device=DEV),
+                          ("hidden", "channels", "lags", "trigger", "weight", "f_window", "form", "state"),
+                          ("acc", "wsum", "cnt", "sig_sum", "sig_sq", "total_rows")),
+}
+
+
+@pytest.mark.parametrize("kind", sorted(SAVED))
+def test_saved_file_keys_and_round_trip(batch, kind, tmp_path):
+    make, top_keys, state_keys = SAVED[kind]
+    t = make()
+    if kind == "label_association":
+        t.update(batch["code3"], torch.arange(N_UTT * T, device=DEV).reshape(N_UTT, T) % 4 - 1, frame_mask=batch["mask3"])
+    elif kind == "triggered_average":
+        t.update(batch["code3"], batch["signal3"], frame_mask=batch["mask3"])
+    else:
+        t.update(batch["code3"], frame_mask=batch["mask3"])
+    t.save(tmp_path / "t.pt")
+    data = torch.load(tmp_path / "t.pt", map_location="cpu", weights_only=True)
+    assert tuple(data) == top_keys and tuple(data["state"]) == state_keys
+    assert all(v is None or v.device.type == "cpu" for v in data["state"].values())
+    assert [name for name, v in data["state"].items() if v is None] == (
+        ["gap_hist", "ev_int", "ev_flt", "ev_count"] if kind == "run_tracker_bare" else [])
+    back = type(t).load(tmp_path / "t.pt", device=DEV)
+    assert tuple(back._state) == state_keys
+    for name, v in t._state.items():
+        w = back._state[name]
+        assert (v is None and w is None) or (v.dtype == w.dtype and v.device == w.device and torch.equal(v, w)), name
+    for attr in ("_form", "_submitted", "_next", "_records"):
+        assert getattr(back, attr, None) == getattr(t, attr, None), attr
+    assert int(t._state[state_keys[0]].ne(0).sum()) > 0  # (a state that has seen the batch)

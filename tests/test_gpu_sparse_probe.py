@@ -432,6 +432,36 @@ def test_fit_reaches_the_reference_optimum(features, weighted):
     np.testing.assert_allclose(gb0.cpu().numpy(), ob / n, rtol=0, atol=1e-6)
 
 
+def test_a_dense_subset_is_planned_twice():
+    """``add_data`` guesses the size of the plan from the subset's share of the dictionary; here every row holds all of the
+    subset, the plan names more entries than the guess and is transposed again at the true count."""
+    code, col_of, P = PB.dense_subset_case()
+    C, l2 = 3, 1e-2
+    rows, k = PB.DENSE_UTT * PB.DENSE_T, PB.DENSE_K
+    flat = (code[0].reshape(rows, k), code[1].reshape(rows, k))
+    seg = np.repeat(np.arange(PB.DENSE_UTT), PB.DENSE_T).astype(np.int32)
+    rng = np.random.default_rng(61)
+    labels = rng.integers(-1, C, rows).astype(np.int32)
+    ent = PB.entries(flat, seg, PB.DENSE_HIDDEN, col_of)
+    pl = PB.plan(ent, P)
+    nnz, guess = int(pl[0][-1]), 1024 + 2 * rows * k * P // PB.DENSE_HIDDEN
+    assert guess == 1280 and nnz == rows * k == 16384 > guess  # the precondition, from the oracle's plan
+    probe = SparseProbe(PB.DENSE_HIDDEN, C, features=torch.tensor(PB.DENSE_FEATURES), l2=l2, device=DEV)
+    probe.add_data((dev(code[0]), dev(code[1])), dev(labels.reshape(PB.DENSE_UTT, PB.DENSE_T)))
+    sh = probe._shards[0]
+    assert probe.n_shards == 1 and sh["nnz"] == nnz and sh["t_row"].numel() == nnz == sh["t_val"].numel()
+    same_plan((sh["col_ptr"].cpu().numpy(), sh["t_row"].cpu().numpy(), sh["t_val"].cpu().numpy(), sh["nnz"]), pl)
+    loss, gW, gb = probe.loss_and_grad()
+    y = PB.row_labels(seg, labels, rows, C, 0)
+    n = int((y >= 0).sum())
+    zero = PB.mirror32(flat, ent, y, np.zeros((P, C), np.float32), np.zeros(C, np.float32), C)
+    np.testing.assert_allclose(float(loss), PB.loss_q(zero["row_loss"]) / 2 ** 20 / n, rtol=0, atol=1e-6)
+    oW, ob = PB.backward(pl, zero["err"], C)
+    np.testing.assert_allclose(gW.cpu().numpy(), oW / n, rtol=0, atol=1e-6)
+    np.testing.assert_allclose(gb.cpu().numpy(), ob / n, rtol=0, atol=1e-6)
+    assert n > 1000 and np.abs(oW / n).max() > 1e-3  # (the gradient is not the trivial one)
+
+
 # ---- 8: the Python layer on real modules --------------------------------------------------------------------------------------
 D, H, K, UTT, T, C_PY = 32, 128, 8, 12, 40, 4
 

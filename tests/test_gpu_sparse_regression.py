@@ -337,6 +337,28 @@ def test_moments_equal_the_oracle(lag):
     same_bits(reg.gram().cpu().numpy(), RG.mirror_upper(s["G"]))
 
 
+def test_a_dense_subset_is_planned_twice():
+    """``update`` guesses the size of the plan from the subset's share of the dictionary; here every row holds all of the
+    subset, the plan names more entries than the guess and is transposed again at the true count."""
+    code, col_of, P = PB.dense_subset_case()
+    C = 2
+    rows, k = PB.DENSE_UTT * PB.DENSE_T, PB.DENSE_K
+    flat = (code[0].reshape(rows, k), code[1].reshape(rows, k))
+    seg = np.repeat(np.arange(PB.DENSE_UTT), PB.DENSE_T).astype(np.int32)
+    Y = RG.targets(np.random.default_rng(62), rows, C)
+    s = RG.statistics(flat, seg, Y, 0, PB.DENSE_HIDDEN, col_of, P)
+    nnz, guess = int(s["pl"][0][-1]), 1024 + 2 * rows * k * P // PB.DENSE_HIDDEN
+    assert guess == 1280 and nnz > guess and nnz == k * int(s["used"].sum())  # the precondition, from the oracle's plan
+    reg = SparseRegression(PB.DENSE_HIDDEN, C, features=torch.tensor(PB.DENSE_FEATURES), device=DEV)
+    reg.update((dev(code[0]), dev(code[1])), dev(Y.reshape(PB.DENSE_UTT, PB.DENSE_T, C)))
+    same_bits(reg.gram().cpu().numpy(), RG.mirror_upper(s["G"]))
+    same_bits(reg.moment.cpu().numpy(), s["MX"][:, :-1])
+    same_bits(reg.col_sum.cpu().numpy(), s["MX"][:, -1])
+    same_bits(reg.target_sum.cpu().numpy(), s["gb"][:-1])
+    assert reg.n_frames == int(s["used"].sum()) > 1500
+    np.testing.assert_allclose(reg.target_sq.cpu().numpy(), s["syy"], rtol=rows * EPS)
+
+
 # ---- 4: the solve, the correlations, the curve --------------------------------------------------------------------------------
 def tracker_of(code, seg, Y, hidden, C, features=None, lag=0):
     reg = SparseRegression(hidden, C, features=None if features is None else torch.as_tensor(features), lag=lag, device=DEV)

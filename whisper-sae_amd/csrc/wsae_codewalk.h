@@ -1,8 +1,12 @@
-// What the analysis kernels that walk a compact (values, indices) code share: the LDS pointer
-// types, the per-segment row bounds of a call, the entry-per-thread walk (CodeArgs, pf_first_active) and the host-side
-// checks on a code and its feature window.  Included by wsae_groupstats.hip (pooling), wsae_runs.hip, wsae_sta.hip,
+// What the analysis kernels that walk a compact (values, indices) code share.  Device side: the LDS
+// pointer types, the per-segment row bounds of a call, the entry-per-thread walk (CodeArgs, pf_first_active) and the
+// wave-per-row front end (probe_row_columns, probe_load_row).  Host side: the predicates behind the *_workspace_bytes
+// queries (code_args_ok for a code with a feature window, column_code_ok for one with a column map) and the CW_REQUIRE_*
+// checks of the entry points: k, rows, window, hidden, the column code, a single lag, the entry lists of a transposed plan,
+// the size of the workspace and its alignment.  Included by wsae_groupstats.hip (pooling), wsae_runs.hip, wsae_sta.hip,
 // wsae_profile.hip and wsae_labels.hip (the entry-per-thread walk), wsae_probe.hip and wsae_regress.hip (the wave-per-row
-// front end) and, for the checks, wsae_coact.hip.
+// front end, the column code) and, for the checks alone, wsae_coact.hip.  (align256 and min64 live in wsae_common.h:
+// wsae_match.hip needs them and walks no code.)
 #pragma once
 #include <limits.h>
 
@@ -134,13 +138,39 @@ inline bool code_args_ok(int64_t n_rows, int k, int max_k, int hidden, int64_t f
            f_lo + f_cols <= hidden;
 }
 
-// FN: the entry point's name, a string literal.  Three macros, not one: every entry point has checks of its own between
-// them, and the order of the checks decides which message a caller with two mistakes gets.
+// the same for a code read through a column map (col_of, or the identity) of P columns
+inline bool column_code_ok(int64_t n_rows, int k, int hidden, int64_t P) {
+    return n_rows >= 0 && n_rows <= INT_MAX && k >= 1 && k <= WSAE_PROBE_MAX_K && hidden >= 1 && P >= 1 && P <= hidden;
+}
+
+inline bool lag_ok(int lag) { return lag >= -1024 && lag <= 1024; }
+
+// FN: the entry point's name, a string literal.  One macro per requirement, not one per entry point: every entry point
+// has checks of its own between them, and the order of the checks decides which message a caller with two mistakes gets.
 #define CW_REQUIRE_K(FN, k, max_k) WSAE_REQUIRE((k) >= 1 && (k) <= (max_k), FN ": need 1 <= k <= %d (got %d)", max_k, k)
 #define CW_REQUIRE_ROWS(FN, n_rows)                                                                                       \
     WSAE_REQUIRE((n_rows) >= 0 && (n_rows) <= INT_MAX, FN ": need 0 <= n_rows <= 2^31 - 1 (got %lld)", (long long)(n_rows))
 #define CW_REQUIRE_WINDOW(FN, f_lo, f_cols, hidden)                                                                       \
     WSAE_REQUIRE((f_lo) >= 0 && (f_cols) >= 1 && (int64_t)(f_lo) + (f_cols) <= (hidden),                                  \
                  FN ": the window [%d, %d + %d) is outside [0, %d)", f_lo, f_lo, f_cols, hidden)
+#define CW_REQUIRE_HIDDEN(FN, hidden) WSAE_REQUIRE((hidden) >= 1, FN ": hidden must be positive (got %d)", hidden)
+#define CW_REQUIRE_COLUMN_CODE(FN, k, hidden, n_rows, col_of, n_cols)                                                     \
+    CW_REQUIRE_K(FN, k, WSAE_PROBE_MAX_K);                                                                                \
+    CW_REQUIRE_HIDDEN(FN, hidden);                                                                                        \
+    CW_REQUIRE_ROWS(FN, n_rows);                                                                                          \
+    WSAE_REQUIRE((n_cols) >= 1 && (n_cols) <= (hidden), FN ": need 1 <= n_cols <= hidden = %d (got %d)", hidden, n_cols); \
+    WSAE_REQUIRE((col_of) || (n_cols) == (hidden), FN ": without col_of the columns are the %d features (got n_cols %d)", \
+                 hidden, n_cols)
+#define CW_REQUIRE_LAG(FN, lag) WSAE_REQUIRE(lag_ok(lag), FN ": need -1024 <= lag <= 1024 (got %d)", lag)
+// the entry lists of a transposed plan (wsae_probe_plan): cap entries of t_row and t_val
+#define CW_REQUIRE_LISTS(FN, cap, t_row, t_val)                                                                           \
+    WSAE_REQUIRE((cap) >= 0 && (((t_row) && (t_val)) || (cap) == 0), FN ": cap %lld entries need t_row and t_val",        \
+                 (long long)(cap))
+// need bytes of workspace; no rows need none, a null workspace counts as 0 bytes
+#define CW_REQUIRE_WORKSPACE(FN, workspace, workspace_bytes, need, n_rows)                                                \
+    WSAE_REQUIRE((workspace_bytes) >= (need) && ((workspace) || (n_rows) == 0), FN ": workspace too small (%lld < %lld)", \
+                 (long long)((workspace) ? (workspace_bytes) : 0), (long long)(need))
+#define CW_REQUIRE_ALIGNED8(FN, workspace)                                                                                \
+    WSAE_REQUIRE(((uintptr_t)(workspace) & 7) == 0, FN ": the workspace must be 8-byte aligned")
 
 }  // namespace

@@ -50,6 +50,9 @@ typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 
 static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
+// the size of a workspace section of b >= 0 bytes: sections start on 256-byte boundaries
+static inline int64_t align256(int64_t b) { return (b + 255) & ~(int64_t)255; }
+__host__ __device__ __forceinline__ int64_t min64(int64_t a, int64_t b) { return a < b ? a : b; }
 
 // number of partial-sum slots every reduction in the library uses (one per producing block,
 // blocks beyond it fold round-robin): fixed so that the reduction order is deterministic.

@@ -109,7 +109,7 @@ extern "C" int wsae_label_update(const float* vals, const int32_t* idx, int32_t 
                                  int64_t* pair_rows, void* workspace, int64_t workspace_bytes, void* stream) {
     WSAE_REQUIRE(vals && idx && labels && cnt && pair_rows, "wsae_label_update: null pointer");
     CW_REQUIRE_K("wsae_label_update", k, WSAE_LABEL_MAX_K);
-    WSAE_REQUIRE(hidden >= 1, "wsae_label_update: hidden must be positive (got %d)", hidden);
+    CW_REQUIRE_HIDDEN("wsae_label_update", hidden);
     CW_REQUIRE_ROWS("wsae_label_update", n_rows);
     CW_REQUIRE_WINDOW("wsae_label_update", f_lo, f_cols, hidden);
     WSAE_REQUIRE(n_classes >= 1 && n_classes <= WSAE_LABEL_MAX_CLASSES, "wsae_label_update: need 1 <= n_classes <= %d (got %d)",

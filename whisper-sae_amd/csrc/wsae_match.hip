@@ -33,8 +33,6 @@ struct MatchPlan {
     int64_t off_a, off_b, off_cv, off_ci, total;
 };
 
-inline int64_t mt_align(int64_t v) { return (v + 255) / 256 * 256; }
-
 // false: arguments outside the documented range (no message: the callers word their own)
 bool mt_plan(int64_t rows_a, int64_t rows_b, int dim, int top_n, int precision, MatchPlan* p) {
     if (rows_a < 1 || rows_b < 1 || rows_a > INT_MAX - 256 || rows_b > INT_MAX - 256) return false;
@@ -53,10 +51,10 @@ bool mt_plan(int64_t rows_a, int64_t rows_b, int dim, int top_n, int precision, 
     p->tps = (p->ctiles + want - 1) / want;
     p->nsplit = (p->ctiles + p->tps - 1) / p->tps;
     p->off_a = 0;
-    p->off_b = mt_align(p->off_a + p->rows_a_pad * p->ldw * esz);
-    p->off_cv = mt_align(p->off_b + p->rows_b_pad * p->ldw * esz);
-    p->off_ci = mt_align(p->off_cv + p->rows_a_pad * p->nsplit * p->nb * 4);
-    p->total = mt_align(p->off_ci + p->rows_a_pad * p->nsplit * p->nb * 4);
+    p->off_b = align256(p->off_a + p->rows_a_pad * p->ldw * esz);
+    p->off_cv = align256(p->off_b + p->rows_b_pad * p->ldw * esz);
+    p->off_ci = align256(p->off_cv + p->rows_a_pad * p->nsplit * p->nb * 4);
+    p->total = align256(p->off_ci + p->rows_a_pad * p->nsplit * p->nb * 4);
     return true;
 }
 

@@ -168,8 +168,6 @@ __global__ __launch_bounds__(1024) void probe_offsets_kernel(const void* __restr
     }
 }
 
-int64_t pb_align(int64_t b) { return (b + 255) & ~(int64_t)255; }
-
 struct PlanWs {
     int64_t chunk_rows;
     int n_chunks;
@@ -183,23 +181,11 @@ PlanWs plan_ws(int64_t n_rows, int P) {
     w.n_chunks = (int)ceil_div64(n_rows, w.chunk_rows);
     if (w.n_chunks < 1) w.n_chunks = 1;
     w.off_table = 0;
-    w.off_lens = w.off_table + pb_align(4 * (int64_t)w.n_chunks * P);
-    w.bytes = w.off_lens + pb_align(4 * (int64_t)P);
+    w.off_lens = w.off_table + align256(4 * (int64_t)w.n_chunks * P);
+    w.bytes = w.off_lens + align256(4 * (int64_t)P);
     return w;
 }
 
-inline bool probe_code_ok(int64_t n_rows, int k, int hidden, int64_t P, bool identity) {
-    return n_rows >= 0 && n_rows <= INT_MAX && k >= 1 && k <= WSAE_PROBE_MAX_K && hidden >= 1 && P >= 1 && P <= hidden &&
-           (!identity || P == hidden);
-}
-
-#define PB_REQUIRE_CODE(FN, k, hidden, n_rows, col_of, n_cols)                                                            \
-    CW_REQUIRE_K(FN, k, WSAE_PROBE_MAX_K);                                                                                \
-    WSAE_REQUIRE((hidden) >= 1, FN ": hidden must be positive (got %d)", hidden);                                         \
-    CW_REQUIRE_ROWS(FN, n_rows);                                                                                          \
-    WSAE_REQUIRE((n_cols) >= 1 && (n_cols) <= (hidden), FN ": need 1 <= n_cols <= hidden = %d (got %d)", hidden, n_cols); \
-    WSAE_REQUIRE((col_of) || (n_cols) == (hidden), FN ": without col_of the columns are the %d features (got n_cols %d)", \
-                 hidden, n_cols)
 #define PB_REQUIRE_CLASSES(FN, C)                                                                                         \
     WSAE_REQUIRE((C) >= 1 && (C) <= WSAE_PROBE_MAX_CLASSES, FN ": need 1 <= n_classes <= %d (got %d)",                    \
                  WSAE_PROBE_MAX_CLASSES, C)
@@ -364,8 +350,6 @@ __global__ __launch_bounds__(PB_FWD_BLOCK) void probe_forward_kernel(FwdArgs a) 
 }
 
 // ---- the backward product ---------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int64_t pb_min64(int64_t a, int64_t b) { return a < b ? a : b; }
-
 // job_ptr [P + 1]: the (column, chunk) jobs before column p.  part [jobs][C]: the chain of job (p, q) over the entries
 // q CHUNK .. of column p, started at 0.
 __global__ __launch_bounds__(64) void probe_partial_kernel(const int64_t* __restrict__ col_ptr, const int32_t* __restrict__ t_row,
@@ -385,9 +369,9 @@ __global__ __launch_bounds__(64) void probe_partial_kernel(const int64_t* __rest
             if (job_ptr[mid] <= jb) lo = mid; else hi = mid;
         }
         const int p = lo;
-        const int64_t end_p = pb_min64(col_ptr[p + 1], cap);
-        const int64_t beg = pb_min64(col_ptr[p], cap) + (jb - job_ptr[p]) * PB_CHUNK;
-        const int64_t end = pb_min64(beg + PB_CHUNK, end_p);
+        const int64_t end_p = min64(col_ptr[p + 1], cap);
+        const int64_t beg = min64(col_ptr[p], cap) + (jb - job_ptr[p]) * PB_CHUNK;
+        const int64_t end = min64(beg + PB_CHUNK, end_p);
         double acc = 0.0;
         for (int64_t i0 = beg; i0 < end; i0 += 64) {
             int er = -1, ev = 0;  // 64 entries of the list, one per lane
@@ -395,7 +379,7 @@ __global__ __launch_bounds__(64) void probe_partial_kernel(const int64_t* __rest
                 er = t_row[i0 + lane];
                 ev = __float_as_int(t_val[i0 + lane]);
             }
-            const int n = (int)pb_min64(64, end - i0);
+            const int n = (int)min64(64, end - i0);
 #pragma unroll
             for (int u0 = 0; u0 < 64; u0 += PB_RB) {
                 if (u0 >= n) break;  // (wave-uniform)
@@ -439,7 +423,7 @@ __global__ __launch_bounds__(64) void probe_bias_partial_kernel(const float* __r
         const int64_t ch = job / c_tiles;
         const int c = (int)(job - ch * c_tiles) * 64 + lane;
         if (c >= C) continue;
-        const int64_t r_lo = ch * PB_CHUNK, r_hi = pb_min64(r_lo + PB_CHUNK, n_rows);
+        const int64_t r_lo = ch * PB_CHUNK, r_hi = min64(r_lo + PB_CHUNK, n_rows);
         double acc = 0.0;
         for (int64_t r0 = r_lo; r0 < r_hi; r0 += PB_RB) {
             float x[PB_RB];
@@ -472,29 +456,27 @@ BwdWs bwd_ws(int64_t n_rows, int P, int C, int64_t cap) {
     w.max_jobs = (int64_t)P + cap / PB_CHUNK;  // every column one ragged piece at most, and the full pieces
     w.row_chunks = ceil_div64(n_rows, PB_CHUNK);
     w.off_jobs = 0;
-    w.off_part = w.off_jobs + pb_align(8 * ((int64_t)P + 1));
-    w.off_bpart = w.off_part + pb_align(8 * w.max_jobs * C);
-    w.bytes = w.off_bpart + pb_align(8 * w.row_chunks * C);
+    w.off_part = w.off_jobs + align256(8 * ((int64_t)P + 1));
+    w.off_bpart = w.off_part + align256(8 * w.max_jobs * C);
+    w.bytes = w.off_bpart + align256(8 * w.row_chunks * C);
     return w;
 }
 
 }  // namespace
 
 extern "C" int64_t wsae_probe_plan_workspace_bytes(int64_t n_rows, int32_t k, int32_t hidden, int32_t n_cols) {
-    return probe_code_ok(n_rows, k, hidden, n_cols, false) ? plan_ws(n_rows, n_cols).bytes : -1;
+    return column_code_ok(n_rows, k, hidden, n_cols) ? plan_ws(n_rows, n_cols).bytes : -1;
 }
 
 extern "C" int wsae_probe_plan(const float* vals, const int32_t* idx, int32_t k, int32_t hidden, const int32_t* seg,
                                int64_t n_rows, const int32_t* col_of, int32_t n_cols, int64_t* col_ptr, int32_t* t_row,
                                float* t_val, int64_t cap, int64_t* nnz, void* workspace, int64_t workspace_bytes, void* stream) {
     WSAE_REQUIRE(vals && idx && col_ptr && nnz, "wsae_probe_plan: null pointer");
-    PB_REQUIRE_CODE("wsae_probe_plan", k, hidden, n_rows, col_of, n_cols);
-    WSAE_REQUIRE(cap >= 0 && ((t_row && t_val) || cap == 0), "wsae_probe_plan: cap %lld entries need t_row and t_val",
-                 (long long)cap);
+    CW_REQUIRE_COLUMN_CODE("wsae_probe_plan", k, hidden, n_rows, col_of, n_cols);
+    CW_REQUIRE_LISTS("wsae_probe_plan", cap, t_row, t_val);
     const PlanWs w = plan_ws(n_rows, n_cols);
-    WSAE_REQUIRE(workspace_bytes >= w.bytes && (workspace || n_rows == 0), "wsae_probe_plan: workspace too small (%lld < %lld)",
-                 (long long)(workspace ? workspace_bytes : 0), (long long)w.bytes);
-    WSAE_REQUIRE(((uintptr_t)workspace & 7) == 0, "wsae_probe_plan: the workspace must be 8-byte aligned");
+    CW_REQUIRE_WORKSPACE("wsae_probe_plan", workspace, workspace_bytes, w.bytes, n_rows);
+    CW_REQUIRE_ALIGNED8("wsae_probe_plan", workspace);
     if (n_rows == 0) return WSAE_OK;
     hipStream_t st = (hipStream_t)stream;
     int32_t* table = (int32_t*)((char*)workspace + w.off_table);
@@ -514,10 +496,9 @@ extern "C" int wsae_probe_plan(const float* vals, const int32_t* idx, int32_t k,
 
 extern "C" int64_t wsae_probe_forward_workspace_bytes(int64_t n_rows, int32_t k, int32_t hidden, int32_t n_cols,
                                                       int32_t n_classes, int32_t lag) {
-    return probe_code_ok(n_rows, k, hidden, n_cols, false) && n_classes >= 1 && n_classes <= WSAE_PROBE_MAX_CLASSES &&
-                   lag >= -1024 && lag <= 1024
-               ? 0
-               : -1;
+    const bool ok =
+        column_code_ok(n_rows, k, hidden, n_cols) && n_classes >= 1 && n_classes <= WSAE_PROBE_MAX_CLASSES && lag_ok(lag);
+    return ok ? 0 : -1;
 }
 
 extern "C" int wsae_probe_forward(const float* vals, const int32_t* idx, int32_t k, int32_t hidden, const int32_t* seg,
@@ -526,9 +507,9 @@ extern "C" int wsae_probe_forward(const float* vals, const int32_t* idx, int32_t
                                   float* err, int64_t lde, float* row_loss, int64_t* n_used, int64_t* n_correct, int64_t* loss_q,
                                   int64_t* confusion, void* workspace, int64_t workspace_bytes, void* stream) {
     WSAE_REQUIRE(vals && idx && labels && W && bias && n_used && n_correct && loss_q, "wsae_probe_forward: null pointer");
-    PB_REQUIRE_CODE("wsae_probe_forward", k, hidden, n_rows, col_of, n_cols);
+    CW_REQUIRE_COLUMN_CODE("wsae_probe_forward", k, hidden, n_rows, col_of, n_cols);
     PB_REQUIRE_CLASSES("wsae_probe_forward", n_classes);
-    WSAE_REQUIRE(lag >= -1024 && lag <= 1024, "wsae_probe_forward: need -1024 <= lag <= 1024 (got %d)", lag);
+    CW_REQUIRE_LAG("wsae_probe_forward", lag);
     WSAE_REQUIRE(ldw >= n_classes, "wsae_probe_forward: ldw %lld is smaller than the %d classes", (long long)ldw, n_classes);
     WSAE_REQUIRE(!err || lde >= n_classes, "wsae_probe_forward: lde %lld is smaller than the %d classes", (long long)lde,
                  n_classes);
@@ -563,13 +544,11 @@ extern "C" int wsae_probe_backward(const int64_t* col_ptr, const int32_t* t_row,
     CW_REQUIRE_ROWS("wsae_probe_backward", n_rows);
     WSAE_REQUIRE(n_cols >= 1, "wsae_probe_backward: n_cols must be positive (got %d)", n_cols);
     PB_REQUIRE_CLASSES("wsae_probe_backward", n_classes);
-    WSAE_REQUIRE(cap >= 0 && ((t_row && t_val) || cap == 0), "wsae_probe_backward: cap %lld entries need t_row and t_val",
-                 (long long)cap);
+    CW_REQUIRE_LISTS("wsae_probe_backward", cap, t_row, t_val);
     WSAE_REQUIRE(lde >= n_classes, "wsae_probe_backward: lde %lld is smaller than the %d classes", (long long)lde, n_classes);
     const BwdWs w = bwd_ws(n_rows, n_cols, n_classes, cap);
-    WSAE_REQUIRE(workspace_bytes >= w.bytes && (workspace || n_rows == 0), "wsae_probe_backward: workspace too small (%lld < %lld)",
-                 (long long)(workspace ? workspace_bytes : 0), (long long)w.bytes);
-    WSAE_REQUIRE(((uintptr_t)workspace & 7) == 0, "wsae_probe_backward: the workspace must be 8-byte aligned");
+    CW_REQUIRE_WORKSPACE("wsae_probe_backward", workspace, workspace_bytes, w.bytes, n_rows);
+    CW_REQUIRE_ALIGNED8("wsae_probe_backward", workspace);
     if (n_rows == 0) return WSAE_OK;
     hipStream_t st = (hipStream_t)stream;
     int64_t* job_ptr = (int64_t*)((char*)workspace + w.off_jobs);

@@ -258,7 +258,7 @@ extern "C" int wsae_profile_update(const float* vals, const int32_t* idx, int32_
     WSAE_REQUIRE(vals && idx && fires && hist && max_bits && min_bits && over && sum_q && total_rows,
                  "wsae_profile_update: null pointer");
     CW_REQUIRE_K("wsae_profile_update", k, WSAE_PROFILE_MAX_K);
-    WSAE_REQUIRE(hidden >= 1, "wsae_profile_update: hidden must be positive (got %d)", hidden);
+    CW_REQUIRE_HIDDEN("wsae_profile_update", hidden);
     CW_REQUIRE_ROWS("wsae_profile_update", n_rows);
     CW_REQUIRE_WINDOW("wsae_profile_update", f_lo, f_cols, hidden);
     WSAE_REQUIRE(workspace_bytes >= 0, "wsae_profile_update: workspace_bytes must not be negative (got %lld)",
@@ -293,7 +293,7 @@ extern "C" int wsae_sample_update(const float* vals, const int32_t* idx, int32_t
                                   void* workspace, int64_t workspace_bytes, void* stream) {
     WSAE_REQUIRE(vals && idx && keys && svals && seen, "wsae_sample_update: null pointer");
     CW_REQUIRE_K("wsae_sample_update", k, WSAE_PROFILE_MAX_K);
-    WSAE_REQUIRE(hidden >= 1, "wsae_sample_update: hidden must be positive (got %d)", hidden);
+    CW_REQUIRE_HIDDEN("wsae_sample_update", hidden);
     CW_REQUIRE_ROWS("wsae_sample_update", n_rows);
     WSAE_REQUIRE(n_rows * k <= INT_MAX, "wsae_sample_update: at most 2^31 - 1 entries per call (got %lld rows of %d)",
                  (long long)n_rows, k);
@@ -308,8 +308,7 @@ extern "C" int wsae_sample_update(const float* vals, const int32_t* idx, int32_t
                  "wsae_sample_update: the ordinals %lld + [0, %lld) leave [0, 2^31)", (long long)ord_base, (long long)n_rows);
     const int64_t n = n_rows * k, n_lists = (int64_t)f_cols * n_strata;
     const int64_t head = sample_head_bytes(n_lists), need = head + 12 * n;
-    WSAE_REQUIRE(workspace_bytes >= need && (workspace || n_rows == 0), "wsae_sample_update: workspace too small (%lld < %lld)",
-                 (long long)(workspace ? workspace_bytes : 0), (long long)need);
+    CW_REQUIRE_WORKSPACE("wsae_sample_update", workspace, workspace_bytes, need, n_rows);
     if (n_rows == 0) return WSAE_OK;
     hipStream_t st = (hipStream_t)stream;
     int32_t* cnt = (int32_t*)workspace;

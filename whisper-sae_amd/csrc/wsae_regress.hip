@@ -41,8 +41,6 @@ constexpr int RF_STATS = 5;
 static_assert(GR_TILE_WIDE % GR_BLOCK == 0 && GR_TILE_MID % GR_BLOCK == 0 && GR_TILE_NARROW % GR_BLOCK == 0,
               "a tile is a whole number of block passes");
 
-__device__ __forceinline__ int64_t rg_min64(int64_t a, int64_t b) { return a < b ? a : b; }
-
 // ---- the Gram matrix --------------------------------------------------------------------------------------------------------
 struct GramArgs {
     const float* vals;
@@ -69,7 +67,7 @@ __device__ __forceinline__ void gram_walk_chunk(const GramArgs& a, int p, int64_
             er = a.t_row[i0 + lane];
             ev = __float_as_int(a.t_val[i0 + lane]);
         }
-        const int n = (int)rg_min64(64, e - i0);
+        const int n = (int)min64(64, e - i0);
         for (int u0 = 0; u0 < n; u0 += GR_ROWS) {
             float v0[GR_ROWS], v1[GR_ROWS];
             int c0[GR_ROWS], c1[GR_ROWS];
@@ -131,7 +129,7 @@ __global__ __launch_bounds__(GR_BLOCK) void gram_kernel(GramArgs a) {
     constexpr int PER = TILE / GR_BLOCK;  // cells of a tile per thread
     for (int pp = blockIdx.x; pp < a.p_rows; pp += gridDim.x) {
         const int p = a.p_lo + pp;
-        const int64_t beg = rg_min64(a.col_ptr[p], a.cap), end = rg_min64(a.col_ptr[p + 1], a.cap);
+        const int64_t beg = min64(a.col_ptr[p], a.cap), end = min64(a.col_ptr[p + 1], a.cap);
         if (end <= beg) continue;  // a column without entries touches nothing (block-uniform)
         const int64_t n_chunks = (end - beg + RG_CHUNK - 1) / RG_CHUNK;
         double* grow = a.G + (int64_t)pp * a.ldg;
@@ -149,10 +147,10 @@ __global__ __launch_bounds__(GR_BLOCK) void gram_kernel(GramArgs a) {
                 if (q < n_chunks) {  // (wave-uniform)
                     for (int c = lo - c_lo + lane; c < hi - c_lo; c += 64) acc[c] = 0.0;
                     const int64_t b = beg + q * RG_CHUNK;
-                    gram_walk_chunk(a, p, b, rg_min64(b + RG_CHUNK, end), c_lo, lo, hi, acc, lane);
+                    gram_walk_chunk(a, p, b, min64(b + RG_CHUNK, end), c_lo, lo, hi, acc, lane);
                 }
                 __syncthreads();
-                const int nw = (int)rg_min64(GR_WAVES, n_chunks - q0);
+                const int nw = (int)min64(GR_WAVES, n_chunks - q0);
 #pragma unroll
                 for (int j = 0; j < PER; ++j) {
                     const int c = c_lo + j * GR_BLOCK + tid;
@@ -169,18 +167,6 @@ __global__ __launch_bounds__(GR_BLOCK) void gram_kernel(GramArgs a) {
         }
     }
 }
-
-inline bool regress_code_ok(int64_t n_rows, int k, int hidden, int64_t P) {
-    return n_rows >= 0 && n_rows <= INT_MAX && k >= 1 && k <= WSAE_PROBE_MAX_K && hidden >= 1 && P >= 1 && P <= hidden;
-}
-
-#define RG_REQUIRE_CODE(FN, k, hidden, n_rows, col_of, n_cols)                                                            \
-    CW_REQUIRE_K(FN, k, WSAE_PROBE_MAX_K);                                                                                \
-    WSAE_REQUIRE((hidden) >= 1, FN ": hidden must be positive (got %d)", hidden);                                         \
-    CW_REQUIRE_ROWS(FN, n_rows);                                                                                          \
-    WSAE_REQUIRE((n_cols) >= 1 && (n_cols) <= (hidden), FN ": need 1 <= n_cols <= hidden = %d (got %d)", hidden, n_cols); \
-    WSAE_REQUIRE((col_of) || (n_cols) == (hidden), FN ": without col_of the columns are the %d features (got n_cols %d)", \
-                 hidden, n_cols)
 
 // ---- the forward product ----------------------------------------------------------------------------------------------------
 struct RfArgs {
@@ -239,7 +225,7 @@ __global__ __launch_bounds__(64) void regress_forward_kernel(RfArgs a, int c_til
         const int c = tile * 64 + lane;
         const bool has_c = c < a.C;
         const double b = has_c ? a.bias[c] : 0.0;
-        const int64_t r_lo = ch * RG_CHUNK, r_hi = rg_min64(r_lo + RG_CHUNK, a.n_rows);
+        const int64_t r_lo = ch * RG_CHUNK, r_hi = min64(r_lo + RG_CHUNK, a.n_rows);
         double s_y = 0.0, s_yy = 0.0, s_p = 0.0, s_pp = 0.0, s_e = 0.0;
         unsigned long long used = 0;
         // the segment and the entries of the next row are requested before the wave works on the current one
@@ -313,17 +299,15 @@ __global__ __launch_bounds__(64) void regress_stats_sum_kernel(const double* __r
     stats[i] = x;
 }
 
-int64_t rg_align(int64_t b) { return (b + 255) & ~(int64_t)255; }
+int64_t gram_ws_half(int64_t n_rows, int k) { return align256(4 * n_rows * k); }  // ccol, then cval
 
-int64_t gram_ws_half(int64_t n_rows, int k) { return rg_align(4 * n_rows * k); }  // ccol, then cval
-
-int64_t forward_ws_bytes(int64_t n_rows, int C) { return rg_align(8 * ceil_div64(n_rows, RG_CHUNK) * RF_STATS * C); }
+int64_t forward_ws_bytes(int64_t n_rows, int C) { return align256(8 * ceil_div64(n_rows, RG_CHUNK) * RF_STATS * C); }
 
 }  // namespace
 
 extern "C" int64_t wsae_gram_workspace_bytes(int64_t n_rows, int32_t k, int32_t hidden, int32_t n_cols, int32_t p_rows,
                                              int64_t cap) {
-    return regress_code_ok(n_rows, k, hidden, n_cols) && n_cols <= WSAE_GRAM_MAX_COLS && p_rows >= 1 && p_rows <= n_cols &&
+    return column_code_ok(n_rows, k, hidden, n_cols) && n_cols <= WSAE_GRAM_MAX_COLS && p_rows >= 1 && p_rows <= n_cols &&
                    cap >= 0
                ? 2 * gram_ws_half(n_rows, k)
                : -1;
@@ -334,17 +318,15 @@ extern "C" int wsae_gram_update(const float* vals, const int32_t* idx, int32_t k
                                 const int32_t* t_row, const float* t_val, int64_t cap, int32_t p_lo, int32_t p_rows, double* G,
                                 int64_t ldg, void* workspace, int64_t workspace_bytes, void* stream) {
     WSAE_REQUIRE(vals && idx && col_ptr && G, "wsae_gram_update: null pointer");
-    RG_REQUIRE_CODE("wsae_gram_update", k, hidden, n_rows, col_of, n_cols);
+    CW_REQUIRE_COLUMN_CODE("wsae_gram_update", k, hidden, n_rows, col_of, n_cols);
     WSAE_REQUIRE(n_cols <= WSAE_GRAM_MAX_COLS, "wsae_gram_update: need n_cols <= %d (got %d)", WSAE_GRAM_MAX_COLS, n_cols);
-    WSAE_REQUIRE(cap >= 0 && ((t_row && t_val) || cap == 0), "wsae_gram_update: cap %lld entries need t_row and t_val",
-                 (long long)cap);
+    CW_REQUIRE_LISTS("wsae_gram_update", cap, t_row, t_val);
     WSAE_REQUIRE(p_lo >= 0 && p_rows >= 1 && (int64_t)p_lo + p_rows <= n_cols,
                  "wsae_gram_update: the row window [%d, %d + %d) is outside [0, %d)", p_lo, p_lo, p_rows, n_cols);
     WSAE_REQUIRE(ldg >= n_cols, "wsae_gram_update: ldg %lld is smaller than the %d columns", (long long)ldg, n_cols);
     const int64_t half = gram_ws_half(n_rows, k);
-    WSAE_REQUIRE(workspace_bytes >= 2 * half && (workspace || n_rows == 0), "wsae_gram_update: workspace too small (%lld < %lld)",
-                 (long long)(workspace ? workspace_bytes : 0), (long long)(2 * half));
-    WSAE_REQUIRE(((uintptr_t)workspace & 7) == 0, "wsae_gram_update: the workspace must be 8-byte aligned");
+    CW_REQUIRE_WORKSPACE("wsae_gram_update", workspace, workspace_bytes, 2 * half, n_rows);
+    CW_REQUIRE_ALIGNED8("wsae_gram_update", workspace);
     if (n_rows == 0) return WSAE_OK;
     GramArgs a = {vals, idx, seg, col_of, col_ptr, t_row, t_val, G, (int32_t*)workspace, (float*)((char*)workspace + half),
                   n_rows, cap, ldg, k, hidden, n_cols, p_lo, p_rows};
@@ -361,8 +343,7 @@ extern "C" int wsae_gram_update(const float* vals, const int32_t* idx, int32_t k
 
 extern "C" int64_t wsae_regress_forward_workspace_bytes(int64_t n_rows, int32_t k, int32_t hidden, int32_t n_cols,
                                                         int32_t n_targets, int32_t lag) {
-    return regress_code_ok(n_rows, k, hidden, n_cols) && n_targets >= 1 && n_targets <= WSAE_PROBE_MAX_CLASSES && lag >= -1024 &&
-                   lag <= 1024
+    return column_code_ok(n_rows, k, hidden, n_cols) && n_targets >= 1 && n_targets <= WSAE_PROBE_MAX_CLASSES && lag_ok(lag)
                ? forward_ws_bytes(n_rows, n_targets)
                : -1;
 }
@@ -373,10 +354,10 @@ extern "C" int wsae_regress_forward(const float* vals, const int32_t* idx, int32
                                     float* pred, int64_t ldp, int64_t* n_used, double* stats, void* workspace,
                                     int64_t workspace_bytes, void* stream) {
     WSAE_REQUIRE(vals && idx && W && bias, "wsae_regress_forward: null pointer");
-    RG_REQUIRE_CODE("wsae_regress_forward", k, hidden, n_rows, col_of, n_cols);
+    CW_REQUIRE_COLUMN_CODE("wsae_regress_forward", k, hidden, n_rows, col_of, n_cols);
     WSAE_REQUIRE(n_targets >= 1 && n_targets <= WSAE_PROBE_MAX_CLASSES, "wsae_regress_forward: need 1 <= n_targets <= %d (got %d)",
                  WSAE_PROBE_MAX_CLASSES, n_targets);
-    WSAE_REQUIRE(lag >= -1024 && lag <= 1024, "wsae_regress_forward: need -1024 <= lag <= 1024 (got %d)", lag);
+    CW_REQUIRE_LAG("wsae_regress_forward", lag);
     WSAE_REQUIRE(ldw >= n_targets, "wsae_regress_forward: ldw %lld is smaller than the %d targets", (long long)ldw, n_targets);
     WSAE_REQUIRE(!pred || ldp >= n_targets, "wsae_regress_forward: ldp %lld is smaller than the %d targets", (long long)ldp,
                  n_targets);
@@ -387,7 +368,7 @@ extern "C" int wsae_regress_forward(const float* vals, const int32_t* idx, int32
     WSAE_REQUIRE(workspace_bytes >= need && (workspace || need == 0 || n_rows == 0),
                  "wsae_regress_forward: workspace too small (%lld < %lld)", (long long)(workspace ? workspace_bytes : 0),
                  (long long)need);
-    WSAE_REQUIRE(((uintptr_t)workspace & 7) == 0, "wsae_regress_forward: the workspace must be 8-byte aligned");
+    CW_REQUIRE_ALIGNED8("wsae_regress_forward", workspace);
     if (n_rows == 0) return WSAE_OK;
     RfArgs a = {vals, idx, seg, Y, col_of, W, bias, pred, (unsigned long long*)n_used, n_rows, ldy, ldw, ldp, k, hidden, lag,
                 n_targets};

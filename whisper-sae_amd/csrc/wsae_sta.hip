@@ -325,8 +325,6 @@ __global__ __launch_bounds__(64) void sta_accum_kernel(const int32_t* __restrict
     }
 }
 
-int64_t sta_align(int64_t b) { return (b + 255) & ~(int64_t)255; }
-
 struct StaPlan {
     int64_t chunk_rows;
     int n_chunks;
@@ -341,12 +339,12 @@ StaPlan sta_plan(int64_t n_rows, int k, int f_cols) {
     if (p.n_chunks < 1) p.n_chunks = 1;
     const int64_t entries = n_rows * k;
     p.off_row = 0;
-    p.off_w = p.off_row + sta_align(4 * entries);
-    p.off_table = p.off_w + sta_align(4 * entries);
-    p.off_lens = p.off_table + sta_align(4 * (int64_t)p.n_chunks * f_cols);
-    p.off_base = p.off_lens + sta_align(4 * (int64_t)f_cols);
-    p.off_order = p.off_base + sta_align(8 * (int64_t)f_cols);
-    p.bytes = p.off_order + sta_align(4 * (int64_t)f_cols);
+    p.off_w = p.off_row + align256(4 * entries);
+    p.off_table = p.off_w + align256(4 * entries);
+    p.off_lens = p.off_table + align256(4 * (int64_t)p.n_chunks * f_cols);
+    p.off_base = p.off_lens + align256(4 * (int64_t)f_cols);
+    p.off_order = p.off_base + align256(8 * (int64_t)f_cols);
+    p.bytes = p.off_order + align256(4 * (int64_t)f_cols);
     return p;
 }
 
@@ -362,7 +360,7 @@ extern "C" int wsae_sta_update(const float* vals, const int32_t* idx, int32_t k,
                                double* wsum, int64_t* cnt, void* workspace, int64_t workspace_bytes, void* stream) {
     WSAE_REQUIRE(vals && idx && y && acc && wsum && cnt, "wsae_sta_update: null pointer");
     CW_REQUIRE_K("wsae_sta_update", k, WSAE_STA_MAX_K);
-    WSAE_REQUIRE(hidden >= 1, "wsae_sta_update: hidden must be positive (got %d)", hidden);
+    CW_REQUIRE_HIDDEN("wsae_sta_update", hidden);
     CW_REQUIRE_ROWS("wsae_sta_update", n_rows);
     WSAE_REQUIRE(y_dtype == WSAE_DT_F32 || y_dtype == WSAE_DT_BF16, "wsae_sta_update: y_dtype must be WSAE_DT_F32 or WSAE_DT_BF16 (got %d)",
                  y_dtype);
@@ -378,9 +376,8 @@ extern "C" int wsae_sta_update(const float* vals, const int32_t* idx, int32_t k,
     WSAE_REQUIRE(weight == WSAE_STA_WEIGHT_VALUE || weight == WSAE_STA_WEIGHT_ONE,
                  "wsae_sta_update: weight must be WSAE_STA_WEIGHT_VALUE or WSAE_STA_WEIGHT_ONE (got %d)", weight);
     const StaPlan p = sta_plan(n_rows, k, f_cols);
-    WSAE_REQUIRE(workspace_bytes >= p.bytes && (workspace || n_rows == 0), "wsae_sta_update: workspace too small (%lld < %lld)",
-                 (long long)(workspace ? workspace_bytes : 0), (long long)p.bytes);
-    WSAE_REQUIRE(((uintptr_t)workspace & 7) == 0, "wsae_sta_update: the workspace must be 8-byte aligned");
+    CW_REQUIRE_WORKSPACE("wsae_sta_update", workspace, workspace_bytes, p.bytes, n_rows);
+    CW_REQUIRE_ALIGNED8("wsae_sta_update", workspace);
     if (n_rows == 0) return WSAE_OK;
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;

@@ -25,7 +25,7 @@ from ..sae.engine import require_device_tensor
 from . import _stream
 
 _METRICS = {"count": N.COACT_COUNT, "cond": N.COACT_COND, "jaccard": N.COACT_JACCARD, "phi": N.COACT_PHI}
-MAX_ROWS = 2 ** 31 - 1  # the marginals and the table cells are int32
+MAX_ROWS = _stream.MAX_ROWS  # the marginals and the table cells are int32 ("rows", not "frames": its own two messages)
 
 
 class CoactivationNeighbors(NamedTuple):

@@ -24,8 +24,6 @@ from .. import _native as N
 from ..sae.engine import require_device_tensor
 from . import _stream
 
-MAX_FRAMES = 2 ** 31 - 1  # seg_rows and the counts are int32
-
 
 class GroupEffects(NamedTuple):
     """Per feature of the window, float64: Cohen's ``d`` (group a minus group b over the pooled standard deviation),
@@ -120,9 +118,7 @@ class SegmentPooler:
         used, rows = n_utt or 0, seg.shape[0]
         if self._next + used > self.n_segments:
             raise ValueError(f"{self._next} + {used} utterances exceed n_segments = {self.n_segments}")
-        if self._submitted + rows > MAX_FRAMES:
-            raise N.WsaeError(f"SegmentPooler: {self._submitted} + {rows} frames exceed {MAX_FRAMES}, the range of the int32 "
-                              f"state")
+        _stream.check_row_bound(self, rows)  # (seg_rows and the counts are int32)
         if rows == 0:
             self._next += used
             return
@@ -277,9 +273,6 @@ def collect_pooled(model, utterances, *, n_segments: Optional[int] = None, f_win
             utterances = list(utterances)
             n_segments = sum((b[0] if isinstance(b, (tuple, list)) else b).shape[0] for b in utterances)
         pooler = SegmentPooler(model.hidden_dim, n_segments, f_window=f_window, counts=counts, device=device)
-        for batch in utterances:
-            x, mask = (batch[0], batch[1]) if isinstance(batch, (tuple, list)) else (batch, None)
-            if x.dim() != 3:
-                raise ValueError(f"an utterance batch must be [n_utt, T, D], got {tuple(x.shape)}")
+        for x, mask in _stream.batches(utterances):
             pooler.update(_stream.utterance_code(model, x, device), frame_mask=None if mask is None else mask.to(device))
     return pooler

@@ -26,7 +26,6 @@ from .. import _native as N
 from . import _stream
 from .profile import ActivationProfile
 
-MAX_ROWS = 2 ** 31 - 1  # a cell of cnt is int32 and takes at most one count per frame
 METRICS = ("precision", "recall", "f1", "jaccard", "phi", "mi", "auroc")
 
 
@@ -179,13 +178,9 @@ class LabelAssociation:
         self.device = self._state["cnt"].device
         return self.device
 
-    def _field(self, name: str) -> Tensor:
-        self._ensure_device()
-        return self._state[name]
-
-    cnt = property(lambda self: self._field("cnt"),
-                   doc="``[f_cols, L, C, S]`` int32: frames on which the feature fired in the stratum, by the label `lag` later.")
-    pair_rows = property(lambda self: self._field("pair_rows"), doc="``[L, C]`` int64: the labelled frame pairs of each lag.")
+    cnt = _stream.state_property(
+        "cnt", "``[f_cols, L, C, S]`` int32: frames on which the feature fired in the stratum, by the label `lag` later.")
+    pair_rows = _stream.state_property("pair_rows", "``[L, C]`` int64: the labelled frame pairs of each lag.")
 
     # ---- accumulation ---------------------------------------------------------------------------
     def update(self, code, labels: Tensor, frame_mask: Optional[Tensor] = None, segments: Optional[Tensor] = None) -> None:
@@ -199,19 +194,13 @@ class LabelAssociation:
         form = _stream.take_form(self, vals)
         seg, _ = _stream.frame_segments(vals, segments, frame_mask, dev)
         rows = seg.shape[0]
-        if labels.shape != vals.shape[:-1] or labels.is_floating_point() or labels.dtype == torch.bool:
-            raise ValueError(f"labels must hold one integer per frame, in the shape {tuple(vals.shape[:-1])} of the code's "
-                             f"frames: got {tuple(labels.shape)} {labels.dtype}")
-        if self._submitted + rows > MAX_ROWS:
-            raise N.WsaeError(f"LabelAssociation: {self._submitted} + {rows} frames exceed {MAX_ROWS}, the range of the int32 "
-                              f"state")
+        _stream.check_frame_labels(vals, labels)
+        _stream.check_row_bound(self, rows)  # (a cell of cnt is int32 and takes at most one count per frame)
         self._form = form
         if rows == 0:
             return
         v, i = _stream.flat_code(vals, idx, k)
-        # (labels beyond int32 are outside every [0, n_classes): -1 keeps them so through the conversion)
-        lab = labels.detach().reshape(-1).to(torch.int64)
-        lab = torch.where((lab >= 0) & (lab < self.n_classes), lab, torch.full_like(lab, -1)).to(torch.int32).contiguous()
+        lab = _stream.frame_labels(vals, labels, self.n_classes)
         st = self._state
         with torch.cuda.device(dev):
             N.check(N.lib().wsae_label_update(
@@ -234,8 +223,7 @@ class LabelAssociation:
         utterances: an integer add."""
         if not self._same_kind(other):
             raise ValueError("merge needs two trackers with the same size, window, classes, lags and edges")
-        if self._submitted + other._submitted > MAX_ROWS:
-            raise N.WsaeError(f"LabelAssociation.merge: {self._submitted} + {other._submitted} frames exceed {MAX_ROWS}")
+        _stream.check_row_bound(self, other._submitted, merging=True)
         if other._state is not None:
             dev = self._ensure_device(other._state["cnt"])
             for name, t in other._state.items():
@@ -298,20 +286,16 @@ class LabelAssociation:
 
     # ---- persistence ----------------------------------------------------------------------------
     def save(self, path) -> None:
-        self._ensure_device()
         torch.save({"hidden": self.hidden, "n_classes": self.n_classes, "lags": [self.lag_lo, self.lag_hi],
                     "f_window": [self.f_lo, self.f_cols], "edges": None if self.edges is None else self.edges.cpu(),
-                    "form": self._form, "submitted": self._submitted,
-                    "state": {name: t.cpu() for name, t in self._state.items()}}, Path(path))
+                    "form": self._form, "submitted": self._submitted, "state": _stream.state_to_cpu(self)}, Path(path))
 
     @classmethod
     def load(cls, path, device=None) -> "LabelAssociation":
         data = torch.load(Path(path), map_location="cpu", weights_only=True)
         a = cls(data["hidden"], data["n_classes"], data["edges"], lags=tuple(data["lags"]), f_window=tuple(data["f_window"]),
                 device=device, max_state_bytes=2 ** 62)
-        a._ensure_device()
-        for name, saved in data["state"].items():
-            a._state[name].copy_(saved)
+        _stream.state_from_saved(a, data["state"])
         a._form, a._submitted = data["form"], int(data["submitted"])
         return a
 
@@ -364,16 +348,6 @@ def automated_labels(assoc: LabelAssociation, class_names: Sequence[str], metric
     return out
 
 
-def _labelled_batches(utterances):
-    for batch in utterances:
-        if not isinstance(batch, (tuple, list)) or len(batch) not in (2, 3):
-            raise ValueError("an item must be (x [n_utt, T, D], labels [n_utt, T]) or (x, labels, frame_mask)")
-        x, labels, mask = batch[0], batch[1], batch[2] if len(batch) == 3 else None
-        if x.dim() != 3:
-            raise ValueError(f"an utterance batch must be [n_utt, T, D], got {tuple(x.shape)}")
-        yield x, labels, mask
-
-
 def collect_label_association(model, utterances, n_classes: int, profile_or_edges: Union[ActivationProfile, Tensor, None] = None,
                               *, n_strata: int = 8, lags: Tuple[int, int] = (0, 0), f_window: Optional[Tuple[int, int]] = None,
                               device="cuda", max_state_bytes: int = 2 ** 31) -> LabelAssociation:
@@ -393,7 +367,7 @@ def collect_label_association(model, utterances, n_classes: int, profile_or_edge
             edges = profile_or_edges
         assoc = LabelAssociation(model.hidden_dim, n_classes, edges, lags=lags, f_window=f_window, device=device,
                                  max_state_bytes=max_state_bytes)
-        for x, labels, mask in _labelled_batches(utterances):
+        for x, labels, mask in _stream.labelled_batches(utterances):
             assoc.update(_stream.utterance_code(model, x, device), labels.to(device),
                          frame_mask=None if mask is None else mask.to(device))
     return assoc

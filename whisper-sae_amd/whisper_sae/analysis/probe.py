@@ -25,9 +25,7 @@ from torch import Tensor
 
 from .. import _native as N
 from . import _stream
-from .labels import _labelled_batches
 
-MAX_ROWS = 2 ** 31 - 1  # rows of one shard (the kernels index a call's rows in int32)
 LOSS_SCALE = float(2 ** 20)  # loss_q counts 2^-20
 
 
@@ -85,14 +83,6 @@ class ProbeData(NamedTuple):
         return self.code, self.labels, keep, self.segments
 
 
-def _frame_labels(vals: Tensor, labels: Tensor, n_classes: int) -> Tensor:
-    if labels.shape != vals.shape[:-1] or labels.is_floating_point() or labels.dtype == torch.bool:
-        raise ValueError(f"labels must hold one integer per frame, in the shape {tuple(vals.shape[:-1])} of the code's "
-                         f"frames: got {tuple(labels.shape)} {labels.dtype}")
-    lab = labels.detach().reshape(-1).to(torch.int64)  # (labels beyond int32 are outside every [0, n_classes))
-    return torch.where((lab >= 0) & (lab < n_classes), lab, torch.full_like(lab, -1)).to(torch.int32).contiguous()
-
-
 class SparseProbe:
     """Softmax regression of ``n_classes`` labels on the features ``features`` (a 1-D index tensor without duplicates;
     None: all ``hidden``) of a compact code.  The label of a frame is read ``lag`` frames later (-1024 .. 1024), never
@@ -108,25 +98,10 @@ class SparseProbe:
             raise ValueError(f"hidden must be positive, got {hidden}")
         if not 1 <= self.n_classes <= N.PROBE_MAX_CLASSES:
             raise ValueError(f"n_classes must be in 1..{N.PROBE_MAX_CLASSES}, got {n_classes}")
-        if not -1024 <= self.lag <= 1024:
-            raise ValueError(f"lag must be in -1024..1024, got {lag}")
+        _stream.check_lag(lag)
         if not self.l2 >= 0:
             raise ValueError(f"l2 must not be negative, got {l2}")
-        if features is None:
-            self.feature_index = torch.arange(self.hidden, dtype=torch.int64)
-            self._col_of = None
-        else:
-            feats = torch.as_tensor(features)
-            if feats.dim() != 1 or feats.numel() < 1 or feats.is_floating_point() or feats.dtype == torch.bool:
-                raise ValueError(f"features must be a 1-D tensor of at least one index, got {tuple(feats.shape)} {feats.dtype}")
-            feats = feats.detach().cpu().to(torch.int64)
-            if int(feats.min()) < 0 or int(feats.max()) >= self.hidden:
-                raise ValueError(f"features must lie in [0, {self.hidden})")
-            if torch.unique(feats).numel() != feats.numel():
-                raise ValueError("features holds an index twice")
-            self.feature_index = feats
-            self._col_of = torch.full((self.hidden,), -1, dtype=torch.int32)
-            self._col_of[feats] = torch.arange(feats.numel(), dtype=torch.int32)
+        self.feature_index, self._col_of = _stream.column_map(features, self.hidden)
         self.n_cols = self.feature_index.numel()
         if class_weight is not None:
             cw = torch.as_tensor(class_weight).detach().to(torch.float32).reshape(-1).cpu()
@@ -167,9 +142,6 @@ class SparseProbe:
         self._ensure_device()
         return self._theta[self.n_cols * self.n_classes:]
 
-    def _workspace(self, nbytes: int, dev) -> Tensor:
-        return _stream.grow(self, max(int(nbytes), 1), torch.uint8, dev)
-
     def _prepare(self, code, labels, frame_mask, segments, check_form: bool):
         vals, idx, k = _stream.compact_code(code, "code", N.PROBE_MAX_K, also=((labels, "labels"),))
         dev = self._ensure_device(vals)
@@ -177,9 +149,9 @@ class SparseProbe:
             raise N.WsaeError(f"the code is on {vals.device} and the labels on {labels.device}, the probe on {dev}")
         form = _stream.take_form(self, vals) if check_form else None
         seg, _ = _stream.frame_segments(vals, segments, frame_mask, dev)
-        lab = _frame_labels(vals, labels, self.n_classes)
-        if seg.shape[0] > MAX_ROWS:
-            raise N.WsaeError(f"SparseProbe: {seg.shape[0]} frames in one shard exceed {MAX_ROWS}")
+        lab = _stream.frame_labels(vals, labels, self.n_classes)
+        if seg.shape[0] > _stream.MAX_ROWS:
+            raise N.WsaeError(f"SparseProbe: {seg.shape[0]} frames in one shard exceed {_stream.MAX_ROWS}")
         v, i = _stream.flat_code(vals, idx, k)
         return v, i, k, seg, lab, form
 
@@ -193,35 +165,14 @@ class SparseProbe:
         rows = seg.shape[0]
         if rows == 0:
             return
-        dev = v.device
-        lib = N.lib()
-        col_ptr = torch.empty(self.n_cols + 1, dtype=torch.int64, device=dev)
-        nnz = torch.zeros(1, dtype=torch.int64, device=dev)
-        need = lib.wsae_probe_plan_workspace_bytes(rows, k, self.hidden, self.n_cols)
-        if need < 0:
-            raise N.WsaeError(f"wsae_probe_plan_workspace_bytes rejects rows={rows} k={k} hidden={self.hidden} cols={self.n_cols}")
-        # first guess: every entry of the code for the full dictionary, the subset's share of them (with room) otherwise
-        cap = rows * k if self._col_of is None else min(rows * k, 1024 + 2 * rows * k * self.n_cols // self.hidden)
-        with torch.cuda.device(dev):
-            for _ in range(2):
-                t_row = torch.empty(cap, dtype=torch.int32, device=dev)
-                t_val = torch.empty(cap, dtype=torch.float32, device=dev)
-                ws = self._workspace(need, dev)
-                N.check(lib.wsae_probe_plan(v.data_ptr(), i.data_ptr(), k, self.hidden, seg.data_ptr(), rows, N.ptr(self._col_of),
-                                            self.n_cols, col_ptr.data_ptr(), N.ptr(t_row), N.ptr(t_val), cap, nnz.data_ptr(),
-                                            ws.data_ptr(), need, torch.cuda.current_stream(dev).cuda_stream), "wsae_probe_plan")
-                n = int(nnz.item())
-                if n <= cap:
-                    break
-                del t_row, t_val
-                cap = n  # (the plan names the true count: grow once and transpose again)
-        if n < cap:
+        col_ptr, t_row, t_val, n = _stream.transposed_plan(self, v, i, k, seg, rows)
+        if n < t_row.numel():  # (the shard keeps its plan: cut it to size)
             t_row, t_val = t_row[:n].clone(), t_val[:n].clone()
         self._shards.append({"v": v, "i": i, "k": k, "seg": seg, "lab": lab, "rows": rows, "col_ptr": col_ptr, "t_row": t_row,
                              "t_val": t_val, "nnz": n})
         if self._err is None or self._err.numel() < rows * self.n_classes:
             self._err = None
-            self._err = torch.empty(rows * self.n_classes, dtype=torch.float32, device=dev)
+            self._err = torch.empty(rows * self.n_classes, dtype=torch.float32, device=v.device)
 
     n_shards = property(lambda self: len(self._shards), doc="The shards added so far.")
 
@@ -254,7 +205,7 @@ class SparseProbe:
             for sh in self._shards:
                 self._forward(sh, W32, b32, self._err, counters, None)
                 need = lib.wsae_probe_backward_workspace_bytes(sh["rows"], P, C, sh["nnz"])
-                ws = self._workspace(need, dev)
+                ws = _stream.workspace(self, need, dev)
                 N.check(lib.wsae_probe_backward(sh["col_ptr"].data_ptr(), N.ptr(sh["t_row"]), N.ptr(sh["t_val"]), sh["nnz"], P,
                                                 self._err.data_ptr(), C, C, sh["rows"], gW.data_ptr(), gb.data_ptr(),
                                                 ws.data_ptr(), need, torch.cuda.current_stream(dev).cuda_stream),
@@ -304,11 +255,8 @@ class SparseProbe:
     def top_weights(self, c: int, n: int = 10) -> Tuple[Tensor, Tensor]:
         """``(features int64, weights float64)``: the ``n`` features with the largest weight for class ``c``, descending,
         ties to the lower column."""
-        if not 0 <= int(c) < self.n_classes:
-            raise ValueError(f"class {c} is outside [0, {self.n_classes})")
-        w = self.weight[:, int(c)]
-        order = _stream.rank_features(w, torch.ones_like(w, dtype=torch.bool), n)
-        return self.feature_index[order], w[order]
+        c = _stream.check_index(c, self.n_classes, "class")
+        return _stream.top_weights(self.weight[:, c], self.feature_index, n)
 
     # ---- persistence ----------------------------------------------------------------------------
     def save(self, path) -> None:
@@ -403,10 +351,7 @@ def sparse_probe_curve(train, test, ranking: Tensor, sizes: Sequence[int] = (1, 
     """The k-sparse probing curve: one probe per size n on the first n features of ``ranking`` (an ordered feature index,
     for example a row of ``top_label_features``).  ``train`` and ``test`` are the argument tuples of ``add_data`` /
     ``evaluate``: ``(code, labels[, frame_mask[, segments]])``.  ``probe_kwargs`` go to ``SparseProbe``."""
-    ranking = torch.as_tensor(ranking).detach().reshape(-1).cpu().to(torch.int64)
-    sizes = tuple(int(s) for s in sizes)
-    if not sizes or min(sizes) < 1 or max(sizes) > ranking.numel():
-        raise ValueError(f"sizes must lie in 1..{ranking.numel()}, the length of the ranking: got {sizes}")
+    ranking, sizes = _stream.curve_arguments(ranking, sizes)
     if "features" in probe_kwargs:
         raise ValueError("sparse_probe_curve chooses the features itself: pass the ranking")
     out = {name: torch.zeros(len(sizes), dtype=torch.float64) for name in ("train_loss", "test_loss", "test_accuracy")}
@@ -428,7 +373,7 @@ def collect_probe_data(model, utterances, device=None) -> ProbeData:
     n_utt = 0
     with _stream.encoding(model, hint="sparse probes are for TopK-family codes"):
         dev = _stream.need_gpu("collect_probe_data", torch.device(device) if device is not None else None)
-        for x, labels, mask in _labelled_batches(utterances):
+        for x, labels, mask in _stream.labelled_batches(utterances):
             v, i = _stream.utterance_code(model, x, dev)
             if labels.shape != x.shape[:2]:
                 raise ValueError(f"labels {tuple(labels.shape)} do not match the frames {tuple(x.shape[:2])}")

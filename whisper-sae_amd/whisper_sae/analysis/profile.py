@@ -26,7 +26,6 @@ from .. import _native as N
 from ..sae.engine import require_device_tensor
 from . import _stream
 
-MAX_ROWS = 2 ** 31 - 1           # fires and the histogram cells are int32, and sum_q holds 2^31 - 1 terms of at most 2^32
 MAX_ORDINALS = 2 ** 31           # a key keeps its ordinal in 31 bits
 PROFILE_BINS = N.PROFILE_BINS
 MIN_INIT = 0x7F800000            # min_bits before anything fired: the bits of +inf
@@ -144,17 +143,13 @@ class ActivationProfile:
         self.device = self._state["fires"].device
         return self.device
 
-    def _field(self, name: str) -> Tensor:
-        self._ensure_device()
-        return self._state[name]
-
-    fires = property(lambda self: self._field("fires"), doc="``[f_cols]`` int32: the rows on which the feature was active.")
-    hist = property(lambda self: self._field("hist"), doc="``[f_cols, 192]`` int32: the value histogram.")
-    max_bits = property(lambda self: self._field("max_bits"), doc="``[f_cols]`` int32: the bits of the largest value.")
-    min_bits = property(lambda self: self._field("min_bits"), doc="``[f_cols]`` int32: the bits of the smallest value.")
-    over = property(lambda self: self._field("over"), doc="``[f_cols]`` int32: the values >= 4096.")
-    sum_q = property(lambda self: self._field("sum_q"), doc="``[f_cols]`` int64: the sum of rint(min(v, 4096) 2^20).")
-    total_rows = property(lambda self: self._field("total_rows"), doc="``[1]`` int64: the non-padding frames seen.")
+    fires = _stream.state_property("fires", "``[f_cols]`` int32: the rows on which the feature was active.")
+    hist = _stream.state_property("hist", "``[f_cols, 192]`` int32: the value histogram.")
+    max_bits = _stream.state_property("max_bits", "``[f_cols]`` int32: the bits of the largest value.")
+    min_bits = _stream.state_property("min_bits", "``[f_cols]`` int32: the bits of the smallest value.")
+    over = _stream.state_property("over", "``[f_cols]`` int32: the values >= 4096.")
+    sum_q = _stream.state_property("sum_q", "``[f_cols]`` int64: the sum of rint(min(v, 4096) 2^20).")
+    total_rows = _stream.state_property("total_rows", "``[1]`` int64: the non-padding frames seen.")
 
     # ---- accumulation ---------------------------------------------------------------------------
     def update(self, code, frame_mask: Optional[Tensor] = None) -> None:
@@ -167,9 +162,8 @@ class ActivationProfile:
         v, i = _stream.flat_code(vals, idx, k)
         rows = v.shape[0]
         seg = _mask_segments(frame_mask, rows, dev)
-        if self._submitted + rows > MAX_ROWS:
-            raise N.WsaeError(f"ActivationProfile: {self._submitted} + {rows} frames exceed {MAX_ROWS}, the range of the "
-                              f"int32 state")
+        # (fires and the histogram cells are int32, and sum_q holds 2^31 - 1 terms of at most 2^32)
+        _stream.check_row_bound(self, rows)
         if rows == 0:
             return
         st = self._state
@@ -186,8 +180,7 @@ class ActivationProfile:
         minimum and a maximum."""
         if (self.hidden, self.f_lo, self.f_cols) != (other.hidden, other.f_lo, other.f_cols):
             raise ValueError("merge needs two profiles of the same size and window")
-        if self._submitted + other._submitted > MAX_ROWS:
-            raise N.WsaeError(f"ActivationProfile.merge: {self._submitted} + {other._submitted} frames exceed {MAX_ROWS}")
+        _stream.check_row_bound(self, other._submitted, merging=True)
         if other._state is None:
             return
         dev = self._ensure_device(other._state["fires"])
@@ -264,17 +257,14 @@ class ActivationProfile:
 
     # ---- persistence ----------------------------------------------------------------------------
     def save(self, path) -> None:
-        self._ensure_device()
         torch.save({"hidden": self.hidden, "f_window": [self.f_lo, self.f_cols], "submitted": self._submitted,
-                    "state": {name: t.cpu() for name, t in self._state.items()}}, Path(path))
+                    "state": _stream.state_to_cpu(self)}, Path(path))
 
     @classmethod
     def load(cls, path, device=None) -> "ActivationProfile":
         data = torch.load(Path(path), map_location="cpu", weights_only=True)
         p = cls(data["hidden"], f_window=tuple(data["f_window"]), device=device)
-        p._ensure_device()
-        for name, saved in data["state"].items():
-            p._state[name].copy_(saved)
+        _stream.state_from_saved(p, data["state"])
         p._submitted = int(data["submitted"])
         return p
 
@@ -351,14 +341,10 @@ class ActivationSampler:
         self.device = self._state["keys"].device
         return self.device
 
-    def _field(self, name: str) -> Tensor:
-        self._ensure_device()
-        return self._state[name]
-
-    keys = property(lambda self: self._field("keys"),
-                    doc="``[f_cols, n_strata, keep]`` int64 holding the uint64 keys, ascending; -1 (2^64 - 1) = unused.")
-    values = property(lambda self: self._field("svals"), doc="``[f_cols, n_strata, keep]`` float32: the values beside the keys.")
-    seen = property(lambda self: self._field("seen"), doc="``[f_cols, n_strata]`` int32: the activations of each stratum.")
+    keys = _stream.state_property("keys",
+                                  "``[f_cols, n_strata, keep]`` int64 holding the uint64 keys, ascending; -1 (2^64 - 1) = unused.")
+    values = _stream.state_property("svals", "``[f_cols, n_strata, keep]`` float32: the values beside the keys.")
+    seen = _stream.state_property("seen", "``[f_cols, n_strata]`` int32: the activations of each stratum.")
 
     # ---- accumulation ---------------------------------------------------------------------------
     def update(self, code, frame_mask: Optional[Tensor] = None) -> None:
@@ -454,30 +440,18 @@ class ActivationSampler:
 
     # ---- persistence ----------------------------------------------------------------------------
     def save(self, path) -> None:
-        self._ensure_device()
         torch.save({"hidden": self.hidden, "f_window": [self.f_lo, self.f_cols], "keep": self.keep, "seed": self.seed,
                     "ordinal_base": self.ordinal_base, "next": self._next, "records": [list(r) for r in self._records],
-                    "edges": None if self.edges is None else self.edges.cpu(),
-                    "state": {name: t.cpu() for name, t in self._state.items()}}, Path(path))
+                    "edges": None if self.edges is None else self.edges.cpu(), "state": _stream.state_to_cpu(self)}, Path(path))
 
     @classmethod
     def load(cls, path, device=None) -> "ActivationSampler":
         data = torch.load(Path(path), map_location="cpu", weights_only=True)
         s = cls(data["hidden"], data["edges"], keep=data["keep"], seed=data["seed"], f_window=tuple(data["f_window"]),
                 ordinal_base=data["ordinal_base"], device=device)
-        s._ensure_device()
-        for name, saved in data["state"].items():
-            s._state[name].copy_(saved)
+        _stream.state_from_saved(s, data["state"])
         s._next, s._records = int(data["next"]), [tuple(r) for r in data["records"]]
         return s
-
-
-def _batches(utterances):
-    for batch in utterances:
-        x, mask = (batch[0], batch[1]) if isinstance(batch, (tuple, list)) else (batch, None)
-        if x.dim() != 3:
-            raise ValueError(f"an utterance batch must be [n_utt, T, D], got {tuple(x.shape)}")
-        yield x, mask
 
 
 def collect_activation_profile(model, utterances, *, device="cuda", **profile_kw) -> ActivationProfile:
@@ -487,7 +461,7 @@ def collect_activation_profile(model, utterances, *, device="cuda", **profile_kw
     previous mode is restored."""
     with _stream.encoding(model, hint="activation profiles are for TopK-family codes"):
         profile = ActivationProfile(model.hidden_dim, device=device, **profile_kw)
-        for x, mask in _batches(utterances):
+        for x, mask in _stream.batches(utterances):
             profile.update(_stream.utterance_code(model, x, device), frame_mask=None if mask is None else mask.to(device))
     return profile
 
@@ -508,6 +482,6 @@ def collect_activation_samples(model, utterances, profile_or_edges: Union[Activa
             edges = profile_or_edges
         sampler = ActivationSampler(model.hidden_dim, edges, keep=keep, seed=seed, f_window=f_window,
                                     ordinal_base=ordinal_base, device=device)
-        for x, mask in _batches(utterances):
+        for x, mask in _stream.batches(utterances):
             sampler.update(_stream.utterance_code(model, x, device), frame_mask=None if mask is None else mask.to(device))
     return sampler

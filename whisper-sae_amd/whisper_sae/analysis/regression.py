@@ -23,9 +23,6 @@ from torch import Tensor
 
 from .. import _native as N
 from . import _stream
-from .labels import _labelled_batches
-
-MAX_ROWS = 2 ** 31 - 1  # rows of one update (the kernels index a call's rows in int32)
 
 
 class RegressionFit(NamedTuple):
@@ -111,9 +108,8 @@ class SparseRegression:
             raise ValueError(f"hidden must be positive, got {hidden}")
         if not 1 <= self.n_targets <= N.PROBE_MAX_CLASSES - 1:  # (the column of ones is one more)
             raise ValueError(f"n_targets must be in 1..{N.PROBE_MAX_CLASSES - 1}, got {n_targets}")
-        if not -1024 <= self.lag <= 1024:
-            raise ValueError(f"lag must be in -1024..1024, got {lag}")
-        self.feature_index, self._col_of = _column_map(features, self.hidden)
+        _stream.check_lag(lag)
+        self.feature_index, self._col_of = _stream.column_map(features, self.hidden)
         self.n_cols = self.feature_index.numel()
         if self.n_cols > N.GRAM_MAX_COLS:
             raise ValueError(f"{self.n_cols} features exceed the {N.GRAM_MAX_COLS} columns of a Gram matrix: pass a subset")
@@ -141,9 +137,6 @@ class SparseRegression:
         self.device = dev
         return dev
 
-    def _workspace(self, nbytes: int, dev) -> Tensor:
-        return _stream.grow(self, max(int(nbytes), 1), torch.uint8, dev)
-
     @property
     def n_frames(self) -> int:
         """The frames used so far (a float64 sum of ones: exact below 2^53)."""
@@ -164,8 +157,8 @@ class SparseRegression:
         else:
             seg, _ = _stream.frame_segments(vals, segments, frame_mask, dev)
         rows = vals.numel() // k
-        if rows > MAX_ROWS:
-            raise N.WsaeError(f"SparseRegression: {rows} frames in one call exceed {MAX_ROWS}")
+        if rows > _stream.MAX_ROWS:
+            raise N.WsaeError(f"SparseRegression: {rows} frames in one call exceed {_stream.MAX_ROWS}")
         Y = None
         if targets is not None:
             if targets.shape != vals.shape[:-1] + (n_targets,) or not targets.is_floating_point():
@@ -201,29 +194,12 @@ class SparseRegression:
         lib = N.lib()
         P, C = self.n_cols, self.n_targets
         E, seg = self._shifted(seg, Y, rows)
-        col_ptr = torch.empty(P + 1, dtype=torch.int64, device=dev)
-        nnz = torch.zeros(1, dtype=torch.int64, device=dev)
-        need = lib.wsae_probe_plan_workspace_bytes(rows, k, self.hidden, P)
-        if need < 0:
-            raise N.WsaeError(f"wsae_probe_plan_workspace_bytes rejects rows={rows} k={k} hidden={self.hidden} cols={P}")
-        cap = rows * k if self._col_of is None else min(rows * k, 1024 + 2 * rows * k * P // self.hidden)
+        col_ptr, t_row, t_val, n = _stream.transposed_plan(self, v, i, k, seg, rows)
         with torch.cuda.device(dev):
             st = torch.cuda.current_stream(dev).cuda_stream
-            for _ in range(2):
-                t_row = torch.empty(cap, dtype=torch.int32, device=dev)
-                t_val = torch.empty(cap, dtype=torch.float32, device=dev)
-                ws = self._workspace(need, dev)
-                N.check(lib.wsae_probe_plan(v.data_ptr(), i.data_ptr(), k, self.hidden, seg.data_ptr(), rows, N.ptr(self._col_of), P,
-                                            col_ptr.data_ptr(), N.ptr(t_row), N.ptr(t_val), cap, nnz.data_ptr(), ws.data_ptr(), need,
-                                            st), "wsae_probe_plan")
-                n = int(nnz.item())
-                if n <= cap:
-                    break
-                del t_row, t_val
-                cap = n  # (the plan names the true count: grow once and transpose again)
             need = max(lib.wsae_gram_workspace_bytes(rows, k, self.hidden, P, P, n),
                        lib.wsae_probe_backward_workspace_bytes(rows, P, C + 1, n))
-            ws = self._workspace(need, dev)
+            ws = _stream.workspace(self, need, dev)
             N.check(lib.wsae_gram_update(v.data_ptr(), i.data_ptr(), k, self.hidden, seg.data_ptr(), rows, N.ptr(self._col_of), P,
                                          col_ptr.data_ptr(), N.ptr(t_row), N.ptr(t_val), n, 0, P, self._G.data_ptr(), P,
                                          ws.data_ptr(), need, st), "wsae_gram_update")
@@ -313,9 +289,7 @@ class SparseRegression:
         feats = fit.features.to(torch.int64)
         if int(feats.min()) < 0 or int(feats.max()) >= self.hidden:
             raise ValueError(f"the fit's features must lie in [0, {self.hidden})")
-        col_of = torch.full((self.hidden,), -1, dtype=torch.int32)
-        col_of[feats] = torch.arange(feats.numel(), dtype=torch.int32)
-        return (col_of.to(dev), fit.weight.to(dev, torch.float64).contiguous(), fit.bias.to(dev, torch.float64).contiguous())
+        return (_stream.column_table(feats, self.hidden).to(dev), fit.weight.to(dev, torch.float64).contiguous(), fit.bias.to(dev, torch.float64).contiguous())
 
     def _forward(self, fit, v, i, k, seg, Y, rows, pred, n_used, stats):
         dev = v.device
@@ -326,7 +300,7 @@ class SparseRegression:
         if need < 0:
             raise N.WsaeError(f"wsae_regress_forward_workspace_bytes rejects rows={rows} k={k} hidden={self.hidden}")
         with torch.cuda.device(dev):
-            ws = self._workspace(need, dev)
+            ws = _stream.workspace(self, need, dev)
             N.check(lib.wsae_regress_forward(v.data_ptr(), i.data_ptr(), k, self.hidden, N.ptr(seg), N.ptr(Y), C, rows, self.lag, C,
                                              col_of.data_ptr(), W.shape[0], W.data_ptr(), C, b.data_ptr(), N.ptr(pred), C,
                                              N.ptr(n_used), N.ptr(stats), ws.data_ptr(), need,
@@ -368,11 +342,8 @@ class SparseRegression:
     def top_weights(self, fit: RegressionFit, c: int, n: int = 10) -> Tuple[Tensor, Tensor]:
         """``(features int64, weights float64)``: the ``n`` features with the largest weight for target ``c``, descending,
         ties to the lower column."""
-        if not 0 <= int(c) < self.n_targets:
-            raise ValueError(f"target {c} is outside [0, {self.n_targets})")
-        w = fit.weight[:, int(c)]
-        order = _stream.rank_features(w, torch.ones_like(w, dtype=torch.bool), n)
-        return fit.features[order], w[order]
+        c = _stream.check_index(c, self.n_targets, "target")
+        return _stream.top_weights(fit.weight[:, c], fit.features, n)
 
     # ---- persistence ----------------------------------------------------------------------------
     def save(self, path) -> None:
@@ -392,32 +363,12 @@ class SparseRegression:
         return s
 
 
-def _column_map(features, hidden: int):
-    """``(feature_index int64, col_of int32 or None)`` on the CPU after the checks on ``features``."""
-    if features is None:
-        return torch.arange(hidden, dtype=torch.int64), None
-    feats = torch.as_tensor(features)
-    if feats.dim() != 1 or feats.numel() < 1 or feats.is_floating_point() or feats.dtype == torch.bool:
-        raise ValueError(f"features must be a 1-D tensor of at least one index, got {tuple(feats.shape)} {feats.dtype}")
-    feats = feats.detach().cpu().to(torch.int64)
-    if int(feats.min()) < 0 or int(feats.max()) >= hidden:
-        raise ValueError(f"features must lie in [0, {hidden})")
-    if torch.unique(feats).numel() != feats.numel():
-        raise ValueError("features holds an index twice")
-    col_of = torch.full((hidden,), -1, dtype=torch.int32)
-    col_of[feats] = torch.arange(feats.numel(), dtype=torch.int32)
-    return feats, col_of
-
-
 def regression_curve(stats: SparseRegression, test, ranking: Tensor, sizes: Sequence[int] = (1, 2, 4, 8, 16, 32, 64),
                      l2: float = 1e-3) -> RegressionCurve:
     """The k-sparse regression curve from ONE accumulated state: per size n the ridge fit on the first n features of
     ``ranking`` (an ordered feature index, all of them among the tracker's features) - a solve of a sub-block - with its
     training R^2 and the R^2 of ``evaluate`` on ``test``, the argument tuple ``(code, targets[, frame_mask[, segments]])``."""
-    ranking = torch.as_tensor(ranking).detach().reshape(-1).cpu().to(torch.int64)
-    sizes = tuple(int(s) for s in sizes)
-    if not sizes or min(sizes) < 1 or max(sizes) > ranking.numel():
-        raise ValueError(f"sizes must lie in 1..{ranking.numel()}, the length of the ranking: got {sizes}")
+    ranking, sizes = _stream.curve_arguments(ranking, sizes)
     where = torch.full((stats.hidden,), -1, dtype=torch.int64)
     where[stats.feature_index.cpu()] = torch.arange(stats.n_cols, dtype=torch.int64)
     if ranking.numel() and (int(ranking.min()) < 0 or int(ranking.max()) >= stats.hidden or bool((where[ranking] < 0).any())):
@@ -434,9 +385,8 @@ def regression_curve(stats: SparseRegression, test, ranking: Tensor, sizes: Sequ
 def top_correlated_features(stats: SparseRegression, c: int, n: int = 10) -> Tuple[Tensor, Tensor]:
     """``(features int64, r float64)``: the ``n`` features whose activation correlates most strongly (by ``|r|``) with target
     ``c``, descending, ties to the lower column; features without variance are no candidates."""
-    if not 0 <= int(c) < stats.n_targets:
-        raise ValueError(f"target {c} is outside [0, {stats.n_targets})")
-    r = stats.correlations()[:, int(c)]
+    c = _stream.check_index(c, stats.n_targets, "target")
+    r = stats.correlations()[:, c]
     _, _, _, var_x, _ = stats._variances()
     order = _stream.rank_features(r.abs(), var_x > 0, n)
     return stats.feature_index[order], r[order]
@@ -451,7 +401,7 @@ def collect_regression(model, utterances, n_targets: int, *, features: Optional[
     with _stream.encoding(model, hint="sparse regression is for TopK-family codes"):
         dev = _stream.need_gpu("collect_regression", torch.device(device) if device is not None else None)
         stats = SparseRegression(model.hidden_dim, n_targets, features=features, lag=lag, device=dev)
-        for x, targets, mask in _labelled_batches(utterances):
+        for x, targets, mask in _stream.labelled_batches(utterances):
             v, i = _stream.utterance_code(model, x, dev)
             stats.update((v, i), targets.to(dev), None if mask is None else mask.to(dev))
     return stats

@@ -26,7 +26,6 @@ from torch import Tensor
 from .. import _native as N
 from . import _stream
 
-MAX_ROWS = 2 ** 31 - 1  # frames, runs and the histogram cells are int32
 RUNS_BINS = N.RUNS_BINS
 
 
@@ -154,22 +153,18 @@ class RunTracker:
         self.device = st["frames"].device
         return self.device
 
-    def _field(self, name: str) -> Tensor:
-        self._ensure_device()
-        return self._state[name]
-
-    frames = property(lambda self: self._field("frames"), doc="``[f_cols]`` int32: the frames on which the feature was active.")
-    runs = property(lambda self: self._field("runs"), doc="``[f_cols]`` int32: the number of runs.")
-    max_run = property(lambda self: self._field("dur_max"), doc="``[f_cols]`` int32: the longest run, in frames.")
-    sum_squares = property(lambda self: self._field("dur_sq"), doc="``[f_cols]`` int64: the sum of the squared run lengths.")
-    duration_hist = property(lambda self: self._field("dur_hist"), doc="``[f_cols, 48]`` int32: the run-length histogram.")
-    total_rows = property(lambda self: self._field("total_rows"), doc="``[1]`` int64: the non-padding frames seen.")
+    frames = _stream.state_property("frames", "``[f_cols]`` int32: the frames on which the feature was active.")
+    runs = _stream.state_property("runs", "``[f_cols]`` int32: the number of runs.")
+    max_run = _stream.state_property("dur_max", "``[f_cols]`` int32: the longest run, in frames.")
+    sum_squares = _stream.state_property("dur_sq", "``[f_cols]`` int64: the sum of the squared run lengths.")
+    duration_hist = _stream.state_property("dur_hist", "``[f_cols, 48]`` int32: the run-length histogram.")
+    total_rows = _stream.state_property("total_rows", "``[1]`` int64: the non-padding frames seen.")
 
     @property
     def gap_hist(self) -> Tensor:
         if not self.with_gaps:
             raise ValueError("this tracker keeps no gap histogram: build it with gaps=True")
-        return self._field("gap_hist")
+        return _stream.state_field(self, "gap_hist")
 
     @property
     def event_count(self) -> int:
@@ -193,8 +188,7 @@ class RunTracker:
         seg, n_utt = _stream.frame_segments(vals, segments, frame_mask, dev)
         used, rows = n_utt or 0, seg.shape[0]
         base, n_seg = self._next, used  # (a flat code: read back below)
-        if self._submitted + rows > MAX_ROWS:
-            raise N.WsaeError(f"RunTracker: {self._submitted} + {rows} frames exceed {MAX_ROWS}, the range of the int32 state")
+        _stream.check_row_bound(self, rows)  # (frames, runs and the histogram cells are int32)
         if rows and n_utt is None:
             base, live = 0, seg >= 0
             hi = int(seg.max().item())
@@ -236,8 +230,7 @@ class RunTracker:
         if None not in (self._form, other._form) and self._form != other._form:
             raise ValueError(f"merge: a tracker of {self._form} updates and one of {other._form} updates number their "
                              f"utterances differently")
-        if self._submitted + other._submitted > MAX_ROWS:
-            raise N.WsaeError(f"RunTracker.merge: {self._submitted} + {other._submitted} frames exceed {MAX_ROWS}")
+        _stream.check_row_bound(self, other._submitted, merging=True)
         if other._state is None:
             return
         dev = self._ensure_device(other._state["frames"])
@@ -301,21 +294,16 @@ class RunTracker:
 
     # ---- persistence ----------------------------------------------------------------------------
     def save(self, path) -> None:
-        self._ensure_device()
-        cpu = {name: None if t is None else t.cpu() for name, t in self._state.items()}
         torch.save({"hidden": self.hidden, "f_window": [self.f_lo, self.f_cols], "gaps": self.with_gaps,
                     "max_events": self.max_events, "min_event_len": self.min_event_len, "next": self._next, "form": self._form,
-                    "submitted": self._submitted, "state": cpu}, Path(path))
+                    "submitted": self._submitted, "state": _stream.state_to_cpu(self)}, Path(path))
 
     @classmethod
     def load(cls, path, device=None) -> "RunTracker":
         data = torch.load(Path(path), map_location="cpu", weights_only=True)
         t = cls(data["hidden"], f_window=tuple(data["f_window"]), gaps=data["gaps"], max_events=data["max_events"],
                 min_event_len=data["min_event_len"], device=device)
-        t._ensure_device()
-        for name, saved in data["state"].items():
-            if saved is not None:
-                t._state[name].copy_(saved)
+        _stream.state_from_saved(t, data["state"])
         t._next, t._submitted, t._form = int(data["next"]), int(data["submitted"]), data["form"]
         return t
 
@@ -340,9 +328,6 @@ def collect_runs(model, utterances, *, device="cuda", **tracker_kw) -> RunTracke
     ``TypeError``) and is run in eval mode; its previous mode is restored."""
     with _stream.encoding(model, hint="run statistics are for TopK-family codes"):
         tracker = RunTracker(model.hidden_dim, device=device, **tracker_kw)
-        for batch in utterances:
-            x, mask = (batch[0], batch[1]) if isinstance(batch, (tuple, list)) else (batch, None)
-            if x.dim() != 3:
-                raise ValueError(f"an utterance batch must be [n_utt, T, D], got {tuple(x.shape)}")
+        for x, mask in _stream.batches(utterances):
             tracker.update(_stream.utterance_code(model, x, device), frame_mask=None if mask is None else mask.to(device))
     return tracker

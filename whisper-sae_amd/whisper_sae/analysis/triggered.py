@@ -24,7 +24,6 @@ from torch import Tensor
 from .. import _native as N
 from . import _stream
 
-MAX_ROWS = 2 ** 31 - 1
 TRIGGERS = {"all": N.STA_TRIGGER_ALL, "onset": N.STA_TRIGGER_ONSET}
 WEIGHTS = {"value": N.STA_WEIGHT_VALUE, "one": N.STA_WEIGHT_ONE}
 _STAT_ROWS = 1 << 16  # rows per step of the baseline sums (bounds the float64 copy of the signal)
@@ -115,16 +114,12 @@ class TriggeredAverageTracker:
         self.device = self._state["acc"].device
         return self.device
 
-    def _field(self, name: str) -> Tensor:
-        self._ensure_device()
-        return self._state[name]
-
-    sums = property(lambda self: self._field("acc"), doc="``[f_cols, L, C]`` float64: the weighted sums of the signal.")
-    weights = property(lambda self: self._field("wsum"), doc="``[f_cols, L]`` float64: the sums of the weights.")
-    counts = property(lambda self: self._field("cnt"), doc="``[f_cols, L]`` int64: the number of terms.")
-    sig_sum = property(lambda self: self._field("sig_sum"), doc="``[C]`` float64: the signal summed over the non-padding frames.")
-    sig_sq = property(lambda self: self._field("sig_sq"), doc="``[C]`` float64: ... and its squares.")
-    total_rows = property(lambda self: self._field("total_rows"), doc="``[1]`` int64: the non-padding frames seen.")
+    sums = _stream.state_property("acc", "``[f_cols, L, C]`` float64: the weighted sums of the signal.")
+    weights = _stream.state_property("wsum", "``[f_cols, L]`` float64: the sums of the weights.")
+    counts = _stream.state_property("cnt", "``[f_cols, L]`` int64: the number of terms.")
+    sig_sum = _stream.state_property("sig_sum", "``[C]`` float64: the signal summed over the non-padding frames.")
+    sig_sq = _stream.state_property("sig_sq", "``[C]`` float64: ... and its squares.")
+    total_rows = _stream.state_property("total_rows", "``[1]`` int64: the non-padding frames seen.")
 
     # ---- accumulation ---------------------------------------------------------------------------
     def update(self, code, signal: Tensor, segments: Optional[Tensor] = None, frame_mask: Optional[Tensor] = None) -> None:
@@ -142,8 +137,8 @@ class TriggeredAverageTracker:
         form = _stream.take_form(self, vals)
         seg, _ = _stream.frame_segments(vals, segments, frame_mask, dev)
         rows = seg.shape[0]
-        if rows > MAX_ROWS:
-            raise N.WsaeError(f"TriggeredAverageTracker: {rows} frames in one update exceed {MAX_ROWS}")
+        if rows > _stream.MAX_ROWS:
+            raise N.WsaeError(f"TriggeredAverageTracker: {rows} frames in one update exceed {_stream.MAX_ROWS}")
         self._form = form
         if rows == 0:
             return
@@ -205,19 +200,16 @@ class TriggeredAverageTracker:
 
     # ---- persistence ----------------------------------------------------------------------------
     def save(self, path) -> None:
-        self._ensure_device()
         torch.save({"hidden": self.hidden, "channels": self.channels, "lags": [self.lag_lo, self.lag_hi],
                     "trigger": self.trigger, "weight": self.weight, "f_window": [self.f_lo, self.f_cols], "form": self._form,
-                    "state": {name: t.cpu() for name, t in self._state.items()}}, Path(path))
+                    "state": _stream.state_to_cpu(self)}, Path(path))
 
     @classmethod
     def load(cls, path, device=None) -> "TriggeredAverageTracker":
         data = torch.load(Path(path), map_location="cpu", weights_only=True)
         t = cls(data["hidden"], data["channels"], lags=tuple(data["lags"]), trigger=data["trigger"], weight=data["weight"],
                 f_window=tuple(data["f_window"]), device=device)
-        t._ensure_device()
-        for name, saved in data["state"].items():
-            t._state[name].copy_(saved)
+        _stream.state_from_saved(t, data["state"])
         t._form = data["form"]
         return t
 
