@@ -110,7 +110,7 @@ struct wsae_ctx {
     float* wg_slabs;      // [WSAE_WGRAD_MAX_SPLIT][2*H*D] split-K partial weight gradients
     float* dbe_slab;      // [WSAE_WGRAD_MAX_SPLIT][H]
     float* dbpre_part;    // [ceil(H/32)][D]
-    uint32_t* ent_pos;    // [maxB*K] bucketed compact code: (feature & 127) << 16 | row-in-chunk
+    uint32_t* ent_pos;    // [maxB*K] bucketed compact code: the entry word of wsae_chunk_sort.h
     void* ent_hid;        // [maxB*K] relu(value) in the contraction dtype, bucket order
     void* ent_dpre;       // [maxB*K] dpre, bucket order
     int32_t* ent_off;     // [ceil(maxB/32)][ceil(H/128)+1] bucket boundaries

@@ -26,6 +26,7 @@
 // Folding the per-row TopK into this kernel (its VALU work under the gather latency) was built and measured: with
 // the two waves per SIMD that 79 KB of LDS per workgroup allow, the TopK's own dependent HBM round trips are as
 // exposed as the gathers (85.6 us fused against 24.7 + 53.2 us separate at cfg 2), so the TopK stays its own launch.
+#include "wsae_chunk_sort.h"
 #include "wsae_common.h"
 #include "wsae_decode_epilogue.h"
 #include "wsae_mfma.h"
@@ -473,7 +474,7 @@ decode_mfma_kernel(const bf16_t* __restrict__ WdT, const float* __restrict__ bd,
             const int e = tid + 512 * j;
             if (e >= nent) continue;
             const int p = atomicAdd(&cur[tl[j]], 1);
-            ent_pos[base + p] = ((uint32_t)(f[j] - tl[j] * tw) << 16) | (uint32_t)(e / K);
+            ent_pos[base + p] = ent_pack(f[j] - tl[j] * tw, e / K);
             ent_hid[base + p] = (bf16_t)(v[j] > 0.f ? v[j] : 0.f);
             ent_dpre[base + p] = (bf16_t)dp[j];
         }

@@ -4,32 +4,32 @@
 //     dW_e = dpre^T (x - b_pre)  -> here dW_e[h,:]  = sum_b dpre[b,h]   * x_c[b,:]
 //     db_e = sum_b dpre ; db_d = sum_b g ; db_pre = db_d - W_e^T db_e
 //
-// Both contractions are [H x B] x [B x D] with a left operand that is 99% zeros and only exists
-// as the compact TopK code (vals, idx)[B,k].  A scatter-add of B*k rows would be atomic-bound
-// (2 x 805 MB of float atomics at cfg2/B=16384 against ~1.3 TB/s); instead each workgroup rebuilds
-// its 128-feature x KT-row slice of the left operand in LDS from the compact code (zero fill +
-// scatter of the entries whose feature falls in the tile) and runs it through the same NT MFMA
-// slab code as the encode GEMM.  The right operands are the transposed batch operands xT / gT
-// left in the ctx by the encode and decode launches.
+// Both contractions are [H x B] x [B x D] with a left operand that is 99% zeros and exists only as the compact TopK code
+// (vals, idx)[B,k].  A scatter-add of B*k rows would be atomic-bound, so a workgroup rebuilds its feature-tile x chunk slice
+// of the left operand in LDS from the code, SORTED per chunk by feature tile (wsae_chunk_sort.h), and runs it on the MFMAs.
+// Split-K over the batch: workgroup id = tile * nsplit + split, so with nsplit = 8 the round-robin workgroup -> XCD dealing
+// puts every tile of one batch range on one XCD, whose L2 then holds that range's dense rows and code.  Every split writes a
+// private fp32 slab; grad_finish_kernel sums the slabs in fixed order (deterministic, no float atomics).
 //
-// Split-K over the batch: workgroup id = tile * nsplit + split, so with nsplit = 8 the round-robin
-// workgroup->XCD dealing puts every tile of one batch range on one XCD, whose 4 MB L2 then holds
-// that range's xT/gT columns and compact code (2048 rows at cfg2 = 3.6 MB): each XCD streams its
-// share of the batch from HBM once and the 144 tiles re-read it from L2.  Every split writes a
-// private fp32 slab; a second kernel sums the slabs in fixed order (deterministic, no float atomics).
+//   kernel                  serves                              code sorted by                       dense operands
+//   wgrad2s_kernel          bf16, D > 256, g left in bf16       the chunked decode launch, else      row-major as they lie: gb, and xb or the
+//                           (the benchmarked route)             bucket_sort_kernel                   caller's rows through the row list
+//   wgrad2_kernel<bf16,1>   the same with WSAE_WGRAD_SPARSE=0   the same                             the same
+//                           (dense MFMA: the A/B partner)
+//   wgrad2_kernel<T,0>      D > 256 otherwise (fp32, fp32 g)    bucket_kernel (tw = 192)             K-contiguous xT / gT, written by the
+//   wgrad_kernel<T,NT>      D <= 256                            bucket_kernel (tw = 128)             stage launch / bucket_kernel's other blocks
+//   wgrad2d_kernel          the ReLU module (no code: dense     -                                    row-major hidden, dpre, xb, gb
+//                           left operand), bf16, D > 256
+// The three 192 x 384 kernels share the tile decode, the row DMA and the epilogue (W2Tile, W2RowDma, w2_epilogue below).
 #include "wsae_common.h"
 #include "wsae_mfma.h"
+#include "wsae_chunk_sort.h"
 
 // ------------------------------------------------------------------------------------------------
-// bucket_kernel, blocks [0, nchunks): per KT-row chunk, counting-sort the chunk's KT*K compact entries by tw-feature tile
-// (tw = 128 for wgrad_kernel, 192 for wgrad2_kernel).
-//   ent_off[chunk][t] .. ent_off[chunk][t+1] : positions (in the flat sorted arrays) of the entries of
-//   tile t;  ent_pos = (feature - t * tw) << 16 | row-in-chunk;  ent_hid = relu(value), ent_dpre = dpre.
-// A (tile, chunk) workgroup of the contraction then touches only its own ~KT*K*128/H entries
-// instead of scanning all KT*K of them for a 128/H hit rate.
+// bucket_kernel: the fallback routes' sort and transposes in one launch.  Blocks [0, nchunks) counting-sort the chunk's
+// KT * K entries by tw-feature tile (layout: wsae_chunk_sort.h), in two batched passes over the code; the blocks after
+// them write the K-contiguous gT (and xT, when no stage launch left it).
 // ------------------------------------------------------------------------------------------------
-#define BUCKET_MAX_TILES 512
-
 template <typename T>
 __global__ void __launch_bounds__(256)
 bucket_kernel(const float* __restrict__ vals, const int32_t* __restrict__ idx, const float* __restrict__ dpre, int B,
@@ -181,7 +181,7 @@ bucket_kernel(const float* __restrict__ vals, const int32_t* __restrict__ idx, c
         for (int j = 0; j < EB; ++j) {
             if (p[j] < 0) continue;
             const int e = e0 + tid + 256 * j;
-            ent_pos[base + p[j]] = ((uint32_t)f[j] << 16) | (uint32_t)(e / K);
+            ent_pos[base + p[j]] = ent_pack(f[j], e / K);
             ent_hid[base + p[j]] = (T)(v[j] > 0.f ? v[j] : 0.f);
             ent_dpre[base + p[j]] = (T)dp[j];
         }
@@ -251,22 +251,19 @@ bucket_sort_kernel(const float* __restrict__ vals, const int32_t* __restrict__ i
         const int e = tid + 1024 * j;
         if (e >= nent) continue;
         const int p = atomicAdd(&cur[tl[j]], 1);
-        ent_pos[base + p] = ((uint32_t)(f[j] - tl[j] * tw) << 16) | (uint32_t)(e / K);
+        ent_pos[base + p] = ent_pack(f[j] - tl[j] * tw, e / K);
         ent_hid[base + p] = (T)(v[j] > 0.f ? v[j] : 0.f);
         ent_dpre[base + p] = (T)dp[j];
     }
 }
 
 // ------------------------------------------------------------------------------------------------
-// wgrad_kernel: one 128-feature x 128-column tile of dW_dT (which = 0) or dW_e (which = 1) over one
-// batch split.  Per KT-row chunk: zero the sparse slice A[buf], scatter the tile's bucketed entries
-// into it, stage the dense slab Bt[buf], MFMA.  A and Bt are double-buffered so that two barriers
-// per chunk suffice: zero(k) may start as soon as every wave has passed the second barrier of chunk
-// k-1 (all reads of buffer k&1 belong to chunk k-2), and the operands of chunk k+1 are fetched into
-// registers while the MFMAs of chunk k run.
+// wgrad_kernel (D <= 256): one 128-feature tile x NT 128-column groups of dW_dT (which = 0) or dW_e (which = 1) over one batch
+// split; 4 * NT waves, wave group g works on columns [d0 + 128 g, d0 + 128 (g + 1)) against the SAME sparse slice.  Per KT-row
+// chunk: zero the slice A[buf], scatter the tile's sorted entries into it, stage the dense slab Bt[buf] (xT / gT), MFMA.  A and
+// Bt are double-buffered so that two barriers per chunk suffice, and the operands of chunk k + 1 are fetched into registers
+// while the MFMAs of chunk k run.
 // ------------------------------------------------------------------------------------------------
-// NT = 128-column groups per workgroup: the workgroup has 4*NT waves, wave group g works on columns
-// [d0 + 128 g, d0 + 128 (g+1)) against the SAME sparse slice, so one zero+scatter feeds NT times the MFMA work.
 template <typename T, int NT>
 __global__ void __launch_bounds__(256 * NT)
 wgrad_kernel(const uint32_t* __restrict__ ent_pos, const T* __restrict__ ent_hid, const T* __restrict__ ent_dpre,
@@ -317,11 +314,7 @@ wgrad_kernel(const uint32_t* __restrict__ ent_pos, const T* __restrict__ ent_hid
     T e_val = (T)0.f;
     // All loads below are unpredicated (indices clamped instead): predicated loads sit behind exec
     // branches, and hipcc then drains every outstanding load (vmcnt(0)) at the next use.
-    auto offsets = [&](int ck) {
-        const int32_t* o = ent_off + (int64_t)min(ck, nchunks - 1) * (ntm + 1) + tm;
-        n_lo = o[0];
-        n_n = o[1] - n_lo;
-    };
+    auto offsets = [&](int ck) { ent_range(ent_off, ck, nchunks, ntm, tm, n_lo, n_n); };
     auto fetch = [&](int ck) {  // entry range of ck must already sit in (n_lo, n_n)
         slab_load_fast<T>(rb, Bt, ldT, d0, D - 1, ck * KT, gtid);  // rows past D repeat row D-1: never stored
         e_lo = n_lo;
@@ -343,10 +336,10 @@ wgrad_kernel(const uint32_t* __restrict__ ent_pos, const T* __restrict__ ent_hid
         slab_store<T>(rb, Bs, gtid);
         __syncthreads();
         const int n = e_n, lo = e_lo;
-        if (tid < n) *(T*)(As + (e_pos >> 16) * LDS_ROW_BYTES + (e_pos & 0xFFFFu) * (int)sizeof(T)) = e_val;
+        if (tid < n) *(T*)(As + ent_feature(e_pos) * LDS_ROW_BYTES + ent_row(e_pos) * (int)sizeof(T)) = e_val;
         for (int e = tid + NTHR; e < n; e += NTHR) {  // buckets beyond one entry per thread (rare)
             const uint32_t p = ent_pos[lo + e];
-            *(T*)(As + (p >> 16) * LDS_ROW_BYTES + (p & 0xFFFFu) * (int)sizeof(T)) = sv[lo + e];
+            *(T*)(As + ent_feature(p) * LDS_ROW_BYTES + ent_row(p) * (int)sizeof(T)) = sv[lo + e];
         }
         if (ck + 1 < c_end) fetch(ck + 1);  // next chunk's operands fly during the MFMAs
         __syncthreads();
@@ -476,6 +469,72 @@ __device__ __forceinline__ void w2_epilogue(char* smem, const f32x16 (&acc)[W2_M
     }
 }
 
+// What a workgroup of wgrad2_kernel, wgrad2s_kernel and wgrad2d_kernel works on.  Workgroup id = tile * nsplit + split (the
+// XCD dealing of the split-K ranges, head of this file); tiles number (matrix, feature tile, column tile); a launch that
+// holds one matrix starts at which0.
+struct W2Tile {
+    int split;             // split-K slot: chunks [c_begin, c_end) of the batch
+    int which;             // 0: dW_dT (hidden, g)   1: dW_e (dpre, x)
+    int tm, tn, f0, d0;    // feature tile and column tile, their first feature and column
+    int nchunks, c_begin, c_end;
+};
+__device__ __forceinline__ W2Tile w2_tile(int nsplit, int ntm, int ntn, int which0) {
+    W2Tile t;
+    t.split = blockIdx.x % nsplit;
+    int tile = blockIdx.x / nsplit;
+    t.which = which0 + tile / (ntm * ntn);
+    tile -= (t.which - which0) * ntm * ntn;
+    t.tm = tile / ntn;
+    t.tn = tile % ntn;
+    t.f0 = t.tm * W2_M;
+    t.d0 = t.tn * W2_N;
+    t.nchunks = t.c_begin = t.c_end = 0;
+    return t;
+}
+// ... and its share of the batch's nchunks chunks
+__device__ __forceinline__ void w2_split_chunks(W2Tile& t, int nsplit, int nchunks) {
+    t.nchunks = nchunks;
+    const int per = (nchunks + nsplit - 1) / nsplit;
+    t.c_begin = t.split * per;
+    t.c_end = min(nchunks, t.c_begin + per);
+}
+
+// The row-major dense operand of wgrad2_kernel<T, true> and wgrad2s_kernel by LDS-DMA: a wave's six pieces of a chunk are the
+// six column blocks of its 8 batch rows, so a lane needs ONE source row per chunk.
+//   load_row(ck)  only LOADS the row-list entry of chunk ck (a chunk ahead of its use);
+//   form_row()    turns it into the pointer, at the top of the next iteration: the wait hipcc puts in front of the first use
+//                 of a loaded value then falls behind that iteration's dma_wait, not into the MFMA phase the load was issued
+//                 from (the hardware counts the asm DMA pieces in the same in-order vmcnt);
+//   piece(..)     issues one of the wave's six pieces of the formed row.
+template <typename T>
+struct W2RowDma {
+    static constexpr int KT = SWZ_ROW_BYTES / (int)sizeof(T);
+    static constexpr int EPC = 16 / (int)sizeof(T);  // elements per 16-byte chunk
+    static_assert(W2_PIECES == W2_N / 64 && W2_WAVES * 8 == 64, "one wave = 8 batch rows of every column block");
+    const T* Bt;            // [B][D] row-major (x: indexed through xrows when given)
+    const int32_t* xrows;
+    int which, B, D, d0, wave, dma_r;
+    uint32_t smem_lds;
+    int rm_c;               // source chunk of this lane's LDS slot
+    int rm_b;               // row-list entry of the chunk the next issue calls fetch
+    const T* rm_src;        // ... and its row
+
+    __device__ __forceinline__ W2RowDma(const T* Bt_, const int32_t* xrows_, int which_, int B_, int D_, int d0_, int wave_, int dma_r_,
+                                        int dma_s, uint32_t smem_lds_)
+        : Bt(Bt_), xrows(xrows_), which(which_), B(B_), D(D_), d0(d0_), wave(wave_), dma_r(dma_r_), smem_lds(smem_lds_),
+          rm_c((dma_s ^ rm_swz(wave_ * 8 + dma_r_)) * EPC), rm_b(0), rm_src(Bt_) {}
+    __device__ __forceinline__ void load_row(int ck) {
+        const int b = min(ck * KT + wave * 8 + dma_r, B - 1);  // rows past the batch repeat its last row (their A columns are zero)
+        rm_b = (which == 1 && xrows) ? xrows[b] : b;
+    }
+    __device__ __forceinline__ void form_row() { rm_src = Bt + (int64_t)rm_b * D; }
+    // piece j of this wave: column block j (64 columns) of batch rows 8 wave .. 8 wave + 7 of the formed row, into stage 0 / 1
+    __device__ __forceinline__ void piece(int stage, int j) const {
+        const int dcol = min(d0 + j * 64 + rm_c, D - EPC);  // column blocks past D repeat the last chunk: never stored
+        glds16(rm_src + dcol, smem_lds + stage * W2_STAGE + W2_A_BYTES + j * 8192 + wave * 1024);
+    }
+};
+
 template <typename T, bool RM>
 __global__ void __launch_bounds__(W2_THREADS)
 wgrad2_kernel(const uint32_t* __restrict__ ent_pos, const T* __restrict__ ent_hid, const T* __restrict__ ent_dpre,
@@ -488,19 +547,13 @@ wgrad2_kernel(const uint32_t* __restrict__ ent_pos, const T* __restrict__ ent_hi
     constexpr int EPC = 16 / (int)sizeof(T);  // elements per 16-byte chunk
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 2, wn = wave & 3;
-    const int split = blockIdx.x % nsplit;
-    int tile = blockIdx.x / nsplit;
-    const int which = which0 + tile / (ntm * ntn);  // 0: dW_dT (hidden, g)   1: dW_e (dpre, x_c)
-    tile -= (which - which0) * ntm * ntn;
-    const int tm = tile / ntn, tn = tile % ntn;
-    const int f0 = tm * W2_M, d0 = tn * W2_N;
+    W2Tile t = w2_tile(nsplit, ntm, ntn, which0);
+    const int split = t.split, which = t.which, tm = t.tm, tn = t.tn, f0 = t.f0, d0 = t.d0;
     const T* Bt = which == 0 ? gT : xT;  // RM: [B][D] row-major (x: indexed through xrows when given)
     const T* sv = which == 0 ? ent_hid : ent_dpre;
     const bool do_dbe = (which == 1) && (tn == 0);
-
-    const int nchunks = (B + KT - 1) / KT;
-    const int per = (nchunks + nsplit - 1) / nsplit;
-    const int c_begin = split * per, c_end = min(nchunks, c_begin + per);
+    w2_split_chunks(t, nsplit, (B + KT - 1) / KT);
+    const int nchunks = t.nchunks, c_begin = t.c_begin, c_end = t.c_end;
 
     f32x16 acc[W2_MI][3];
 #pragma unroll
@@ -512,31 +565,17 @@ wgrad2_kernel(const uint32_t* __restrict__ ent_pos, const T* __restrict__ ent_hi
     // db_e: wave w sums the 16-row tiles w and w + W2_WAVES (12 tiles) with 16x16 MFMAs against ones
     f32x4 rs0 = {0.f, 0.f, 0.f, 0.f}, rs1 = {0.f, 0.f, 0.f, 0.f};
 
-    // per-lane constants of the DMA: piece p = wave + 8 j covers rows 8 p .. 8 p + 7 of the dense slab
-    const int dma_r = lane >> 3, dma_s = lane & 7;
     const uint32_t smem_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
+    const int dma_r = lane >> 3, dma_s = lane & 7;  // per-lane constants of the DMA: a piece is 8 rows of 8 16-byte slots
+    W2RowDma<T> rd(Bt, xrows, which, B, D, d0, wave, dma_r, dma_s, smem_lds);  // RM: the dense operand as it lies in memory
     // dense slab of chunk ck into stage 0 / 1: half of this wave's pieces per call (j0 = 0 or W2_PIECES / 2)
-    // RM: source row of this lane's pieces for the chunk the next dma3 calls fetch (set by rm_row, a chunk ahead)
-    // (rm_row only LOADS the row-list entry; rm_use turns it into the pointer at the top of the next iteration, so the
-    // wait hipcc puts in front of the first use of a loaded value falls behind that iteration's dma_wait, not into the MFMA
-    // phase the load was issued from - the hardware counts the asm DMA pieces in the same in-order vmcnt)
-    const T* rm_src = Bt;
-    int rm_b = 0;
-    const int rm_c = (dma_s ^ rm_swz(wave * 8 + dma_r)) * EPC;  // source chunk of this lane's LDS slot
-    auto rm_row = [&](int ck) {
-        const int b = min(ck * KT + wave * 8 + dma_r, B - 1);  // rows past the batch repeat its last row (their A columns are zero)
-        rm_b = (which == 1 && xrows) ? xrows[b] : b;
-    };
-    auto rm_use = [&]() { rm_src = Bt + (int64_t)rm_b * D; };
     auto dma3 = [&](int ck, int stage, int j0) {
 #pragma unroll
         for (int j = j0; j < j0 + W2_PIECES / 2; ++j) {
             if constexpr (RM) {
-                // piece j of this wave: column block j (64 columns) of batch rows 8 wave .. 8 wave + 7
-                static_assert(!RM || (W2_PIECES == W2_N / 64 && W2_WAVES * 8 == 64), "one wave = 8 batch rows of every column block");
-                const int dcol = min(d0 + j * 64 + rm_c, D - EPC);  // column blocks past D repeat the last chunk: never stored
-                glds16(rm_src + dcol, smem_lds + stage * W2_STAGE + W2_A_BYTES + j * 8192 + wave * 1024);
+                rd.piece(stage, j);
             } else {
+                // K-contiguous operands (xT / gT): piece p = wave + 8 j covers rows 8 p .. 8 p + 7 of the dense slab
                 const int piece = wave + W2_WAVES * j;
                 const int row = piece * 8 + dma_r;
                 const int c = dma_s ^ ((row >> 1) & 7);
@@ -558,11 +597,7 @@ wgrad2_kernel(const uint32_t* __restrict__ ent_pos, const T* __restrict__ ent_hi
     int n_lo = 0, n_n = 0;   // ... and of the chunk after e (offsets run one chunk ahead of the entries)
     uint32_t e_pos = 0, p_pos = 0;
     T e_val = (T)0.f;
-    auto offsets = [&](int ck) {
-        const int32_t* o = ent_off + (int64_t)min(ck, nchunks - 1) * (ntm + 1) + tm;
-        n_lo = o[0];
-        n_n = o[1] - n_lo;
-    };
+    auto offsets = [&](int ck) { ent_range(ent_off, ck, nchunks, ntm, tm, n_lo, n_n); };
     auto entries = [&](int ck) {  // entry range of ck must already sit in (n_lo, n_n)
         p_lo = e_lo; p_n = e_n; p_pos = e_pos;
         e_lo = n_lo;
@@ -586,12 +621,12 @@ wgrad2_kernel(const uint32_t* __restrict__ ent_pos, const T* __restrict__ ent_hi
         offsets(c_begin);
         entries(c_begin);
         if constexpr (RM) {
-            rm_row(c_begin);
-            rm_use();
+            rd.load_row(c_begin);
+            rd.form_row();
         }
         dma3(c_begin, 0, 0);
         dma3(c_begin, 0, W2_PIECES / 2);
-        if constexpr (RM) rm_row(min(c_begin + 1, c_end - 1));
+        if constexpr (RM) rd.load_row(min(c_begin + 1, c_end - 1));
 #pragma unroll
         for (int st = 0; st < 2; ++st)
 #pragma unroll
@@ -608,12 +643,12 @@ wgrad2_kernel(const uint32_t* __restrict__ ent_pos, const T* __restrict__ ent_hi
         char* nxt = smem + (buf ^ 1) * W2_STAGE;
         const bool more = ck + 1 < c_end;
         entries(min(ck + 1, c_end - 1));  // (the last iteration re-reads its own chunk: keeps p_* = this chunk)
-        if constexpr (RM) rm_use();       // row pointer of chunk ck + 1 (its list entry was requested a chunk ago)
+        if constexpr (RM) rd.form_row();  // row pointer of chunk ck + 1 (its list entry was requested a chunk ago)
         // (one call site: two copies of the MFMA phase made hipcc double the accumulators and spill)
         Mfma96<T, W2_MI>::template slab<RM, false, RM>(cur, cur + W2_A_BYTES, wm * 32 * W2_MI, wn * 96, lane, acc, [&](int kk) {
             if (more && kk < 2) dma3(ck + 1, buf ^ 1, kk * (W2_PIECES / 2));  // >= half a phase to land
             if constexpr (RM) {
-                if (kk == 2) rm_row(min(ck + 2, c_end - 1));  // the row list entry of the chunk after next (an L2 hit by then)
+                if (kk == 2) rd.load_row(min(ck + 2, c_end - 1));  // the row list entry of the chunk after next (an L2 hit by then)
             }
         });
         if (do_dbe) {
@@ -671,22 +706,16 @@ wgrad2s_kernel(const uint32_t* __restrict__ ent_pos, const bf16_t* __restrict__ 
                const int32_t* __restrict__ xrows, int which0, int nslots, int dec_row_base) {
     typedef bf16_t T;
     extern __shared__ __attribute__((aligned(1024))) char smem[];  // (slab_sparse takes swizzle bits from LDS addresses)
-    constexpr int KT = 64, EPC = 8;
+    constexpr int KT = 64;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 2, wn = wave & 3;
-    const int split = blockIdx.x % nsplit;
-    int tile = blockIdx.x / nsplit;
-    const int which = which0 + tile / (ntm * ntn);  // 0: dW_dT (hidden, g)   1: dW_e (dpre, x_c)
-    tile -= (which - which0) * ntm * ntn;
-    const int tm = tile / ntn, tn = tile % ntn;
-    const int f0 = tm * W2_M, d0 = tn * W2_N;
+    W2Tile t = w2_tile(nsplit, ntm, ntn, which0);
+    const int split = t.split, which = t.which, tm = t.tm, tn = t.tn, f0 = t.f0, d0 = t.d0;
     const T* Bt = which == 0 ? gT : xT;  // [B][D] row-major (x: indexed through xrows when given)
     const T* sv = which == 0 ? ent_hid : ent_dpre;
     const bool do_dbe = (which == 1) && (tn == 0);
-
-    const int nchunks = (B + KT - 1) / KT;
-    const int per = (nchunks + nsplit - 1) / nsplit;
-    const int c_begin = split * per, c_end = min(nchunks, c_begin + per);
+    w2_split_chunks(t, nsplit, (B + KT - 1) / KT);
+    const int nchunks = t.nchunks, c_begin = t.c_begin, c_end = t.c_end;
 
     f32x16 acc[W2_MI][3];
 #pragma unroll
@@ -697,29 +726,18 @@ wgrad2s_kernel(const uint32_t* __restrict__ ent_pos, const bf16_t* __restrict__ 
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
     f32x4 rs0 = {0.f, 0.f, 0.f, 0.f}, rs1 = {0.f, 0.f, 0.f, 0.f};
 
-    // the dense operand's LDS-DMA: as wgrad2_kernel<T, true>
-    const int dma_r = lane >> 3, dma_s = lane & 7;
     const uint32_t smem_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
-    const T* rm_src = Bt;
-    int rm_b = 0;
-    const int rm_c = (dma_s ^ rm_swz(wave * 8 + dma_r)) * EPC;
-    auto rm_row = [&](int ck) {
-        const int b = min(ck * KT + wave * 8 + dma_r, B - 1);
-        rm_b = (which == 1 && xrows) ? xrows[b] : b;
-    };
-    auto rm_use = [&]() { rm_src = Bt + (int64_t)rm_b * D; };
+    W2RowDma<T> rd(Bt, xrows, which, B, D, d0, wave, lane >> 3, lane & 7, smem_lds);  // the dense operand, as in wgrad2_kernel<T, true>
     auto dma3 = [&](int stage, int j0) {
 #pragma unroll
-        for (int j = j0; j < j0 + W2_PIECES / 2; ++j) {
-            const int dcol = min(d0 + j * 64 + rm_c, D - EPC);
-            glds16(rm_src + dcol, smem_lds + stage * W2_STAGE + W2_A_BYTES + j * 8192 + wave * 1024);
-        }
+        for (int j = j0; j < j0 + W2_PIECES / 2; ++j) rd.piece(stage, j);
     };
 
     uint32_t* const ix_img = (uint32_t*)(smem + W2S_IX_OFF);    // [stage][layer][t][192]
     uint32_t* const bm_img = (uint32_t*)(smem + W2S_BM_OFF);    // [3][192][2]
     uint32_t* const l2mask = (uint32_t*)(smem + W2S_MASK_OFF);  // [stage]
-    // entry p = feature << 16 | row: the bitmap word of its group, and the nibble's shift in it
+    // entry p = feature << 16 | row (the entry word of wsae_chunk_sort.h, taken apart by hand here: its helpers move this
+    // kernel's instructions): the bitmap word of its group, and the nibble's shift in it
     auto bm_word = [&](int bm, uint32_t p) -> uint32_t* { return bm_img + bm * (W2S_BM_BYTES / 4) + (p >> 16) * 2 + ((p >> 5) & 1); };
     auto setbit = [&](int bm, uint32_t p) { atomicOr(bm_word(bm, p), 1u << (((p >> 2) & 7) * 4 + (p & 3))); };
     // the entry with its rank in bits 9:8 (free: the row takes 6 bits).  The bitmap of a chunk is complete one window before
@@ -757,11 +775,7 @@ wgrad2s_kernel(const uint32_t* __restrict__ ent_pos, const bf16_t* __restrict__ 
     int p_lo = 0, p_n = 0, e_lo = 0, e_n = 0, f_lo = 0, f_n = 0, n_lo = 0, n_n = 0;
     uint32_t p_pos = 0, e_pos = 0, f_pos = 0;
     T e_val = (T)0.f;
-    auto offsets = [&](int ck) {
-        const int32_t* o = ent_off + (int64_t)min(ck, nchunks - 1) * (ntm + 1) + tm;
-        n_lo = o[0];
-        n_n = o[1] - n_lo;
-    };
+    auto offsets = [&](int ck) { ent_range(ent_off, ck, nchunks, ntm, tm, n_lo, n_n); };
     auto advance = [&](int ck) {  // at the top of chunk ck: (n_lo, n_n) is the range of chunk ck + 2
         p_lo = e_lo; p_n = e_n; p_pos = e_pos;
         e_lo = f_lo; e_n = f_n; e_pos = f_pos;
@@ -796,11 +810,11 @@ wgrad2s_kernel(const uint32_t* __restrict__ ent_pos, const bf16_t* __restrict__ 
         f_pos = ent_pos[f_lo + min(tid, max(f_n - 1, 0))];
         offsets(c_begin + 1);
         advance(c_begin - 1);
-        rm_row(c_begin);
-        rm_use();
+        rd.load_row(c_begin);
+        rd.form_row();
         dma3(0, 0);
         dma3(0, W2_PIECES / 2);
-        rm_row(min(c_begin + 1, c_end - 1));
+        rd.load_row(min(c_begin + 1, c_end - 1));
 #pragma unroll
         for (int st = 0; st < 2; ++st)
 #pragma unroll
@@ -827,13 +841,13 @@ wgrad2s_kernel(const uint32_t* __restrict__ ent_pos, const bf16_t* __restrict__ 
         advance(ck);
         { const int t = b0; b0 = b1; b1 = b2; b2 = t; }
         e_pos = ranked(b1, e_pos);
-        rm_use();  // row pointer of chunk ck + 1 (its list entry was requested a chunk ago)
+        rd.form_row();  // row pointer of chunk ck + 1 (its list entry was requested a chunk ago)
         const uint32_t m2all = (uint32_t)__builtin_amdgcn_readfirstlane((int)l2mask[buf]);
         Mfma96<T, W2_MI>::template slab_sparse<W2_M>(cur, ix_img + buf * (W2S_IX_BYTES / 4), smem_lds + buf * W2_STAGE + W2_A_BYTES,
                                                      wm * 32 * W2_MI, wn * 96, lane,
                                                      (m2all >> (wm * W2_MI)) & ((1u << W2_MI) - 1u), acc, [&](int kk) {
             if (more && kk < 2) dma3(buf ^ 1, kk * (W2_PIECES / 2));
-            if (kk == 2) rm_row(min(ck + 2, c_end - 1));  // the row list entry of the chunk after next (an L2 hit by then)
+            if (kk == 2) rd.load_row(min(ck + 2, c_end - 1));  // the row list entry of the chunk after next (an L2 hit by then)
         });
         if (do_dbe) {
             Mfma96<T, W2_MI>::rowsum16(cur, wave * 16, lane, rs0);
@@ -869,17 +883,12 @@ wgrad2d_kernel(const bf16_t* __restrict__ hid, const bf16_t* __restrict__ dpre, 
     constexpr int KT = 64, EPC = 8;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 2, wn = wave & 3;
-    const int split = blockIdx.x % nsplit;
-    int tile = blockIdx.x / nsplit;
-    const int which = tile / (ntm * ntn);  // 0: dW_dT (hidden, g)   1: dW_e (dpre, x)
-    tile -= which * ntm * ntn;
-    const int tm = tile / ntn, tn = tile % ntn;
-    const int f0 = tm * W2_M, d0 = tn * W2_N;
+    W2Tile t = w2_tile(nsplit, ntm, ntn, 0);
+    const int split = t.split, which = t.which, f0 = t.f0, d0 = t.d0;
     const bf16_t* Am = which == 0 ? hid : dpre;  // [B][H]
     const bf16_t* Bm = which == 0 ? gb : xb;     // [B][D]
-    const int nchunks = B / KT;
-    const int per = (nchunks + nsplit - 1) / nsplit;
-    const int c_begin = split * per, c_end = min(nchunks, c_begin + per);
+    w2_split_chunks(t, nsplit, B / KT);
+    const int c_begin = t.c_begin, c_end = t.c_end;
 
     f32x16 acc[W2_MI][3];
 #pragma unroll
@@ -923,44 +932,8 @@ wgrad2d_kernel(const bf16_t* __restrict__ hid, const bf16_t* __restrict__ dpre, 
         __syncthreads();  // ... for every wave; and everybody is done reading `cur` (the chunk after next lands there)
     }
 
-    const int64_t rstr = (int64_t)nslots * D;
-    float* dst = out + (which == 0 ? (int64_t)H * rstr : 0) + (int64_t)split * D;
-    const int col = lane & 31, rq = lane >> 5;
-    if (f0 + W2_M <= H && d0 + W2_N <= D) {  // interior tiles: 16-byte stores through an LDS patch (as wgrad2_kernel)
-        constexpr int PSW = 100;
-        float* patch = (float*)smem + wave * 32 * PSW;
-        float* drow = dst + (int64_t)(f0 + wm * 32 * W2_MI) * rstr + d0 + wn * 96;
-#pragma unroll
-        for (int mi = 0; mi < W2_MI; ++mi) {
-#pragma unroll
-            for (int ni = 0; ni < 3; ++ni)
-#pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    patch[((r & 3) + 8 * (r >> 2) + 4 * rq) * PSW + ni * 32 + col] = acc[mi][ni][r];
-            __builtin_amdgcn_wave_barrier();
-#pragma unroll
-            for (int i = 0; i < 12; ++i) {
-                const int idx = lane + 64 * i;
-                const int row = idx / 24, c4 = idx - row * 24;
-                const float4 v = *(const float4*)(patch + row * PSW + c4 * 4);
-                *(float4*)(drow + (int64_t)(mi * 32 + row) * rstr + c4 * 4) = v;
-            }
-            __builtin_amdgcn_wave_barrier();
-        }
-    } else {
-#pragma unroll
-        for (int mi = 0; mi < W2_MI; ++mi)
-#pragma unroll
-            for (int ni = 0; ni < 3; ++ni) {
-                const int d = d0 + wn * 96 + ni * 32 + col;
-                if (d >= D) continue;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int f = f0 + wm * 32 * W2_MI + mi * 32 + (r & 3) + 8 * (r >> 2) + 4 * rq;
-                    if (f < H) dst[(int64_t)f * rstr + d] = acc[mi][ni][r];
-                }
-            }
-    }
+    const f32x4 no_rs = {0.f, 0.f, 0.f, 0.f};  // (no db_e here: the ReLU module sums its own columns)
+    w2_epilogue(smem, acc, no_rs, no_rs, out, nullptr, which, split, f0, d0, wm, wn, wave, lane, H, D, nslots, H, false);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1262,6 +1235,14 @@ static int pick_nsplit(wsae_ctx* ctx, int tiles, int nchunks, int nt, int max_sp
     return best;
 }
 
+// the 192 x 384 kernels (wgrad2_kernel, wgrad2s_kernel, wgrad2d_kernel) serve wide inputs; wgrad_kernel's 128-feature tiles
+// serve D <= 256
+static bool wgrad_wide(const wsae_ctx* ctx) { return ctx->D > 256; }
+// arrival ticket of grad_finish_kernel (ctx->counters, [16..) = the tickets of the one-round kernels)
+static unsigned long long* grad_finish_ticket(const wsae_ctx* ctx) {
+    return (unsigned long long*)(ctx->counters + 16 + 4 * TICKET_WORDS);
+}
+
 // geometry of one wsae_weight_grads call
 struct WgPlan {
     int ldT, nchunks, nt, ntm, ntn, nsplit, nslots, nwhich, which0, dec_row_base;
@@ -1277,7 +1258,7 @@ static WgPlan plan_wgrad(wsae_ctx* ctx, int B, int part) {
     p.ldT = (B + 127) / 128 * 128;
     p.nchunks = ceil_div(B, Mfma<T>::KT);
     const int ncol = ceil_div(D, TILE_N);  // column groups per workgroup: all of D in one workgroup when D is 2 or 3 tiles wide
-    p.v2 = D > 256;                        // wgrad2_kernel (192 x 384 tiles) for wide inputs, the 128-feature kernel serves D <= 256
+    p.v2 = wgrad_wide(ctx);
     p.nt = p.v2 ? 0 : (ncol % 3 == 0) ? 3 : (ncol % 2 == 0) ? 2 : 1;
     p.ntm = p.v2 ? ceil_div(H, W2_M) : ceil_div(H, TILE_M);
     p.ntn = p.v2 ? ceil_div(D, W2_N) : ncol / p.nt;
@@ -1323,26 +1304,19 @@ static void launch_wgrad(wsae_ctx* ctx, const WgPlan& p, hipStream_t st, const f
     WSAE_PROF_BEGIN(ctx, WSAE_K_WGRAD, st);
 #define WG_ARGS ctx->ent_pos, (const T*)ctx->ent_hid, (const T*)ctx->ent_dpre, ctx->ent_off, (const T*)ctx->xT, \
                 (const T*)ctx->gT, B, ldT, ctx->H, ctx->D, p.nsplit, ntm, p.ntn, out, slab_stride, ctx->dbe_slab
-    if (nt == 0) {
-        bool done = false;
-        if constexpr (sizeof(T) == 2) {
-            if (rm) {
-                const T* xsrc = ctx->xT_valid ? (const T*)ctx->xb : (const T*)x;
-                if (ctx->wgrad_sparse)  // the TopK code on the 2:4 sparse MFMA (default; WSAE_WGRAD_SPARSE=0 keeps the dense form)
-                    wgrad2s_kernel<<<grid, W2_THREADS, W2S_LDS_BYTES, st>>>(
-                        ctx->ent_pos, (const bf16_t*)ctx->ent_hid, (const bf16_t*)ctx->ent_dpre, ctx->ent_off, (const bf16_t*)xsrc,
-                        (const bf16_t*)ctx->gb, B, ctx->H, ctx->D, p.nsplit, ntm, p.ntn, out, ctx->dbe_slab,
-                        ctx->xT_valid ? nullptr : rows, p.which0, p.nslots, p.dec_row_base);
-                else
-                    wgrad2_kernel<T, true><<<grid, W2_THREADS, 2 * W2_STAGE, st>>>(
-                        ctx->ent_pos, (const T*)ctx->ent_hid, (const T*)ctx->ent_dpre, ctx->ent_off, xsrc, (const T*)ctx->gb, B, ldT,
-                        ctx->H, ctx->D, p.nsplit, ntm, p.ntn, out, slab_stride, ctx->dbe_slab, ctx->xT_valid ? nullptr : rows,
-                        p.which0, p.nslots, p.dec_row_base);
-                done = true;
-            }
-        }
-        if (!done) wgrad2_kernel<T, false><<<grid, W2_THREADS, 2 * W2_STAGE, st>>>(WG_ARGS, nullptr, p.which0, p.nslots, p.dec_row_base);
-    }
+    // rm (plan_wgrad) implies bf16 and the 192-wide geometry: the row-major kernels are named with bf16_t, so the float
+    // instantiation of this function compiles the same two launches and never reaches them
+    const bf16_t* xsrc = ctx->xT_valid ? (const bf16_t*)ctx->xb : (const bf16_t*)x;
+    const int32_t* xrows = ctx->xT_valid ? nullptr : rows;
+    if (rm && ctx->wgrad_sparse)  // the TopK code on the 2:4 sparse MFMA (default; WSAE_WGRAD_SPARSE=0 keeps the dense form)
+        wgrad2s_kernel<<<grid, W2_THREADS, W2S_LDS_BYTES, st>>>(
+            ctx->ent_pos, (const bf16_t*)ctx->ent_hid, (const bf16_t*)ctx->ent_dpre, ctx->ent_off, xsrc, (const bf16_t*)ctx->gb, B,
+            ctx->H, ctx->D, p.nsplit, ntm, p.ntn, out, ctx->dbe_slab, xrows, p.which0, p.nslots, p.dec_row_base);
+    else if (rm)
+        wgrad2_kernel<bf16_t, true><<<grid, W2_THREADS, 2 * W2_STAGE, st>>>(
+            ctx->ent_pos, (const bf16_t*)ctx->ent_hid, (const bf16_t*)ctx->ent_dpre, ctx->ent_off, xsrc, (const bf16_t*)ctx->gb, B,
+            ldT, ctx->H, ctx->D, p.nsplit, ntm, p.ntn, out, slab_stride, ctx->dbe_slab, xrows, p.which0, p.nslots, p.dec_row_base);
+    else if (nt == 0) wgrad2_kernel<T, false><<<grid, W2_THREADS, 2 * W2_STAGE, st>>>(WG_ARGS, nullptr, p.which0, p.nslots, p.dec_row_base);
     else if (nt == 3) wgrad_kernel<T, 3><<<grid, 768, 2 * 4 * TILE_LDS_BYTES, st>>>(WG_ARGS);
     else if (nt == 2) wgrad_kernel<T, 2><<<grid, 512, 2 * 3 * TILE_LDS_BYTES, st>>>(WG_ARGS);
     else wgrad_kernel<T, 1><<<grid, 256, 2 * 2 * TILE_LDS_BYTES, st>>>(WG_ARGS);
@@ -1353,8 +1327,7 @@ static void launch_wgrad(wsae_ctx* ctx, const WgPlan& p, hipStream_t st, const f
 // feature-tile width and count of the contraction wsae_weight_grads will run on this ctx (the chunked decode kernel sorts
 // the code for it)
 void wsae_internal_wgrad_tiling(const wsae_ctx* c, int* tile_width, int* ntiles) {
-    const bool v2 = c->D > 256;
-    *tile_width = v2 ? W2_M : TILE_M;
+    *tile_width = wgrad_wide(c) ? W2_M : TILE_M;
     *ntiles = ceil_div(c->H, *tile_width);
 }
 
@@ -1369,7 +1342,7 @@ static void launch_grad_finish(wsae_ctx* ctx, const WgPlan& p, hipStream_t st, c
     // reduction blocks: 8 rows each (two per wave), more when nrows / 8 would exceed the number of norm-partial slots
     const int nrb = (int)min((int64_t)WSAE_MAX_PARTIALS - 1, ceil_div64(nrows, 8));
     const int nblk = ceil_div(H, DBPRE_ROWS);
-    unsigned long long* ticket = (unsigned long long*)(ctx->counters + 16 + 4 * TICKET_WORDS);
+    unsigned long long* ticket = grad_finish_ticket(ctx);
     const int grid = nrb + (do_bias ? nblk + DBD_L1 : 0);
 #define GF_ARGS ctx->wg_slabs, ctx->dbe_slab, p.nsplit, bpre, out, o, H, D, ctx->part_sq, nrb, row0, nrows, slab_row0, W, \
                 ctx->dbpre_part, nblk, ctx->part_dbd, ctx->n_dec_blocks, ctx->dbd2, ticket, do_bias, fired_src, 1, \
@@ -1438,7 +1411,7 @@ extern "C" int wsae_weight_grads(wsae_ctx* ctx, const float* params, const void*
     return weight_grads_impl(ctx, params, x, x_dtype, rows, vals, idx, dpre, B, WSAE_PART_ALL, grads, nullptr, 0, (hipStream_t)stream);
 }
 
-extern "C" int wsae_wgrad_parts_supported(const wsae_ctx* ctx) { return (ctx && ctx->D > 256) ? 1 : 0; }
+extern "C" int wsae_wgrad_parts_supported(const wsae_ctx* ctx) { return (ctx && wgrad_wide(ctx)) ? 1 : 0; }
 
 extern "C" int wsae_ctx_set_comm_reserve(wsae_ctx* ctx, int32_t n_cus) {
     WSAE_REQUIRE(ctx && n_cus >= 0 && n_cus < ctx->cus, "wsae_ctx_set_comm_reserve: %d compute units of %d", n_cus, ctx ? ctx->cus : 0);
@@ -1463,7 +1436,7 @@ extern "C" int wsae_weight_grads_wire(wsae_ctx* ctx, const float* params, const 
 int wsae_internal_relu_wgrad(wsae_ctx* ctx, const void* hid, const void* dpre, const void* xb, const void* gb, int B, float* grads,
                              hipStream_t st) {
     const int H = ctx->H, D = ctx->D;
-    if (ctx->prec != WSAE_PREC_BF16 || D <= 256 || D % 8 || H % 8 || B % 64 || B < 64) return 0;
+    if (ctx->prec != WSAE_PREC_BF16 || !wgrad_wide(ctx) || D % 8 || H % 8 || B % 64 || B < 64) return 0;
     const int ntm = ceil_div(H, W2_M), ntn = ceil_div(D, W2_N);
     const int nchunks = B / 64;
     const int nsplit = pick_nsplit(ctx, ntm * ntn * 2, nchunks, 0, WSAE_WGRAD_MAX_SPLIT);
@@ -1474,6 +1447,6 @@ int wsae_internal_relu_wgrad(wsae_ctx* ctx, const void* hid, const void* dpre, c
     const int nrb = (int)min((int64_t)WSAE_MAX_PARTIALS - 2, ceil_div64(2 * (int64_t)H, 8));
     grad_finish_kernel<bf16_t, false, float, WSAE_WGRAD_MAX_SPLIT><<<nrb, 256, 0, st>>>(
         ctx->wg_slabs, ctx->dbe_slab, nsplit, nullptr, grads, o, H, D, ctx->part_sq, nrb, 0, 2 * H, 0, (const bf16_t*)nullptr,
-        ctx->dbpre_part, 0, ctx->part_dbd, 0, ctx->dbd2, (unsigned long long*)(ctx->counters + 16 + 4 * TICKET_WORDS), 0, nullptr, 0);
+        ctx->dbpre_part, 0, ctx->part_dbd, 0, ctx->dbd2, grad_finish_ticket(ctx), 0, nullptr, 0);
     return nrb;
 }
