@@ -876,6 +876,75 @@ int wsae_regress_forward(const float* vals, const int32_t* idx, int32_t k, int32
                          const double* W, int64_t ldw, const double* bias, float* pred, int64_t ldp, int64_t* n_used,
                          double* stats, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- code dynamics: frame similarity and boundary scoring --------------------------------------------
+ * How the code of a frame as a whole moves through time: the similarity of the codes of frames r and r + l straight from
+ * a compact code vals / idx [n_rows, k] (1 <= k <= WSAE_DYN_MAX_K) whose rows are in time order, and the score of a
+ * per-frame boundary curve against reference boundaries at every threshold.  Ctx-free; the caller's stream, no
+ * allocation, no host synchronisation, no float atomics; argument errors are found on the host before any HIP call;
+ * n_rows == 0 returns WSAE_OK and touches nothing; every *_workspace_bytes returns -1 for invalid arguments; workspace
+ * contents are arbitrary on entry.
+ *
+ * Active entries (the rule of wsae_runs_update).  seg int32 [n_rows] (nullable = one segment, no padding): a row with
+ * seg < 0 is padding.  Feature f is active on row r iff the row is not padding and some entry has idx == f, v > 0 (NaN is
+ * not, +inf is) and 0 <= f < hidden; an index repeated within a row counts once, with the value of its first active
+ * entry.  weight fp32 [hidden] (nullable = all 1): the feature's value on the row is u = v weight[f], one fp32 product,
+ * and a feature with weight[f] <= 0 or NaN is active on no row.  Without weight u = v.
+ *
+ * wsae_dyn_update.  lags int32 [n_lags] in HOST memory: ascending, distinct, 1 <= lag <= WSAE_DYN_MAX_LAG,
+ * 1 <= n_lags <= WSAE_DYN_MAX_LAGS.  The pair of (r, lag l) is (r, q = r + l); it is valid iff row r is not padding,
+ * q < n_rows and seg[q] == seg[r] (without seg: iff q < n_rows).  The rows in between are not examined.  With p the
+ * entry positions 0 .. k - 1 of row r in ascending order, restricted to the positions that hold an active feature of r:
+ *   s   = ONE chain of fp64 additions from 0 of double(u_r(f_p)) double(u_q(f_p)) over those p whose feature is active on
+ *         row q as well (the product of two fp32 values is exact in fp64);
+ *   n_r = ONE chain of fp64 additions from 0 of double(u_r(f_p))^2 over all those p (n_q likewise over the positions of q);
+ *   a_r = the number of active features of row r, i = the number of those p that matched.
+ * WSAE_DYN_DOT: s.  WSAE_DYN_COSINE: 0 where n_r == 0 or n_q == 0, else c = s / sqrt(n_r n_q) in fp64 (one product, one
+ * square root, one quotient) and 1 unless c <= 1.  WSAE_DYN_JACCARD: 0 where a_r + a_q - i == 0, else the fp64 quotient
+ * i / (a_r + a_q - i).  The result is rounded once to fp32.  A sequential loop reproduces every bit; the value does not
+ * depend on the launch geometry, on the other lags of the call or on how whole utterances are grouped into calls.
+ *   sim fp32 [n_rows, n_lags] (nullable): the similarity of a valid pair, NaN for an invalid one.
+ *   State (nullable as a whole: pairs, sim_q, sq_q, hist and total_rows all or none; caller-owned, zero-initialised
+ *   device memory; WSAE_DYN_COSINE and WSAE_DYN_JACCARD only - with WSAE_DYN_DOT it is WSAE_ERR_INVALID).  label int32
+ *   [n_rows] (nullable = no frame is labelled; a label < 0 is "unlabelled").  The class of a valid pair: 0 = both frames
+ *   labelled and equal, 1 = both labelled and different, 2 = otherwise.  With x = llrint(double(sim) 2^30) (exact; 0 <= x
+ *   <= 2^30), cell [l][class] of pairs int64 [n_lags, 3] += 1, of sim_q int64 [n_lags, 3] += x, of sq_q int64 [n_lags, 3]
+ *   += (x >> 15)^2, and hist int64 [n_lags, 3, WSAE_DYN_BINS] += 1 at bin min(x >> 24, 63); total_rows int64 [1] += the
+ *   non-padding rows.  Every field is an integer sum: two states add, whatever the order of the calls.
+ * Workspace (8-byte aligned): wsae_dyn_workspace_bytes - the canonical code (8 bytes per entry: u, and f or -1) and 12
+ * bytes per row (n_r, a_r), in sections of 256-byte multiples.
+ *
+ * wsae_boundary_score.  nov fp32 [n_rows]: nov[r] describes the boundary between rows r and r + 1, NaN = undefined.  ref
+ * uint8 [n_rows] (nullable = no references): nonzero = a reference boundary at r.  thr fp32 [n_thr] in DEVICE memory,
+ * 1 <= n_thr <= WSAE_BOUNDARY_MAX_THR, in any order, equal values, infinities and NaN (which predicts nothing) allowed;
+ * 0 <= tol <= WSAE_BOUNDARY_MAX_TOL rows.  A stretch is a maximal run of consecutive rows with equal seg >= 0 (without
+ * seg: the whole call).  Row r of a stretch is a peak iff nov[r] > left and nov[r] >= right, where a neighbour that lies
+ * in another stretch, outside the call or is NaN counts as -inf (so a NaN or -inf row is no peak, and a plateau peaks at
+ * its first row).  At threshold t the predictions of a stretch are its peaks with nov >= t, the references its rows
+ * with ref != 0, and the hits the greedy one-to-one match of the two lists in time order: with p and q the earliest
+ * prediction and reference not yet consumed, |p - q| <= tol is a hit that consumes both, otherwise the earlier of the two
+ * is consumed.  n_pred int64 [n_thr] += the predictions, n_hit int64 [n_thr] += the hits, n_ref int64 [1] += the
+ * references, n_peaks int64 [1] += the peaks (all stretches of the call; integer sums, so calls add); peaks uint8
+ * [n_rows] (nullable) = 1 on a peak and 0 elsewhere, written on every row.  Workspace (8-byte aligned):
+ * wsae_boundary_workspace_bytes - one flag byte and one stretch-list slot of 4 bytes per row, and a counter. */
+#define WSAE_DYN_COSINE 0
+#define WSAE_DYN_DOT 1
+#define WSAE_DYN_JACCARD 2
+#define WSAE_DYN_MAX_K 128
+#define WSAE_DYN_MAX_LAGS 16
+#define WSAE_DYN_MAX_LAG 1024
+#define WSAE_DYN_BINS 64
+#define WSAE_BOUNDARY_MAX_THR 256
+#define WSAE_BOUNDARY_MAX_TOL 64
+int64_t wsae_dyn_workspace_bytes(int64_t n_rows, int32_t k, int32_t hidden, int32_t n_lags);
+int wsae_dyn_update(const float* vals, const int32_t* idx, int32_t k, int32_t hidden, const int32_t* seg, const float* weight,
+                    const int32_t* label, int64_t n_rows, const int32_t* lags, int32_t n_lags, int32_t metric, float* sim,
+                    int64_t* pairs, int64_t* sim_q, int64_t* sq_q, int64_t* hist, int64_t* total_rows, void* workspace,
+                    int64_t workspace_bytes, void* stream);
+int64_t wsae_boundary_workspace_bytes(int64_t n_rows, int32_t n_thr, int32_t tol);
+int wsae_boundary_score(const float* nov, const int32_t* seg, const uint8_t* ref, int64_t n_rows, const float* thr,
+                        int32_t n_thr, int32_t tol, int64_t* n_pred, int64_t* n_hit, int64_t* n_ref, int64_t* n_peaks,
+                        uint8_t* peaks, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,6 +28,9 @@ PROFILE_MAX_K, PROFILE_BINS, SAMPLE_MAX_STRATA, SAMPLE_MAX_KEEP = 128, 192, 16, 
 LABEL_MAX_K, LABEL_MAX_CLASSES, LABEL_MAX_LAGS, LABEL_MAX_STRATA = 128, 1024, 16, 16  # wsae_label_update
 PROBE_MAX_K, PROBE_MAX_CLASSES, PROBE_CHUNK = 128, 1024, 2048  # wsae_probe_plan / wsae_probe_forward / wsae_probe_backward
 GRAM_MAX_COLS = 8192  # wsae_gram_update
+DYN_COSINE, DYN_DOT, DYN_JACCARD = 0, 1, 2  # wsae_dyn_update
+DYN_MAX_K, DYN_MAX_LAGS, DYN_MAX_LAG, DYN_BINS = 128, 16, 1024, 64
+BOUNDARY_MAX_THR, BOUNDARY_MAX_TOL = 256, 64  # wsae_boundary_score
 BTK_STATE_WORDS = 8  # wsae_batch_topk_state: threshold, beta, last_t (f32), saturated_rows, kept, 3 reserved (i32)
 
 
@@ -150,6 +153,10 @@ SIGNATURES = {
     "wsae_regress_forward_workspace_bytes": (_i64, [_i64, _i32, _i32, _i32, _i32, _i32]),
     "wsae_regress_forward": (C.c_int, [_p, _p, _i32, _i32, _p, _p, _i64, _i64, _i32, _i32, _p, _i32, _p, _i64, _p, _p, _i64, _p, _p,
                                        _p, _i64, _p]),
+    "wsae_dyn_workspace_bytes": (_i64, [_i64, _i32, _i32, _i32]),
+    "wsae_dyn_update": (C.c_int, [_p, _p, _i32, _i32, _p, _p, _p, _i64, _p, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _i64, _p]),
+    "wsae_boundary_workspace_bytes": (_i64, [_i64, _i32, _i32]),
+    "wsae_boundary_score": (C.c_int, [_p, _p, _p, _i64, _p, _i32, _i32, _p, _p, _p, _p, _p, _p, _i64, _p]),
     "wsae_relu_needs_hidden":(C.c_int, [_p, _i32]),
     "wsae_relu_forward": (C.c_int, [_p, _p, _p, _i32, _p, _i32, _f32, _p, _p, _p, _p, _p]),
     "wsae_relu_backward": (C.c_int, [_p, _p, _p, _i32, _p, _i32, _f32, _p, _p, _p, _p]),

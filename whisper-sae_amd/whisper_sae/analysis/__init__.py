@@ -6,12 +6,16 @@ features (run lengths, gaps, event lists), feature-triggered averages of a per-f
 value stratum and lag against a per-frame label: precision, recall, F1, phi, mutual information and AUROC at the best
 threshold and lag), and sparse linear probes (softmax regression of a label on the compact code over all or a subset of
 the features, and the k-sparse probing curve), and sparse ridge regression (the Gram matrix of the code and the target
-moments in one streaming pass, then ridge fits of any feature subset as host-side solves).  Mirrors the names of the reference's ``whisper_sae.analysis.feature_viz``
+moments in one streaming pass, then ridge fits of any feature subset as host-side solves), and code dynamics (the
+similarity of a frame's whole code to the code a few frames later, its statistics within and across labels, and the score
+of the curve's peaks against reference boundaries at every threshold).  Mirrors the names of the reference's ``whisper_sae.analysis.feature_viz``
 that sit on that path."""
 
 from .coactivation import (CoactivationNeighbors, CoactivationTracker, collect_coactivation,
                            compare_activations)
 from .dictionary import NearestFeatures, compare_dictionaries, duplicate_features, nearest_features
+from .dynamics import (BoundaryCurve, BoundaryScorer, CodeDynamics, DynamicsSummary, LagStats, boundaries_from_labels,
+                       boundary_curve, collect_code_dynamics, detect_boundaries, frame_similarity, novelty)
 from .feature_viz import FeatureActivation, TopKTracker, collect_top_activations
 from .group_stats import (GroupEffects, SegmentPooler, bootstrap_weights, collect_pooled, group_effect_sizes,
                           top_group_features)
@@ -37,4 +41,6 @@ __all__ = ["FeatureActivation", "TopKTracker", "collect_top_activations", "Neare
            "top_profile_features", "BestLabels", "LabelAssociation", "LabelScores", "automated_labels", "best_labels",
            "collect_label_association", "top_label_features", "ProbeCurve", "ProbeData", "ProbeFit", "ProbeReport", "SparseProbe",
            "collect_probe_data", "sparse_probe_curve", "utterance_split", "RegressionCurve", "RegressionFit", "RegressionReport",
-           "SparseRegression", "collect_regression", "regression_curve", "ridge_from_statistics", "top_correlated_features"]
+           "SparseRegression", "collect_regression", "regression_curve", "ridge_from_statistics", "top_correlated_features",
+           "BoundaryCurve", "BoundaryScorer", "CodeDynamics", "DynamicsSummary", "LagStats", "boundaries_from_labels",
+           "boundary_curve", "collect_code_dynamics", "detect_boundaries", "frame_similarity", "novelty"]
