@@ -945,6 +945,57 @@ int wsae_boundary_score(const float* nov, const int32_t* seg, const uint8_t* ref
                         int32_t n_thr, int32_t tol, int64_t* n_pred, int64_t* n_hit, int64_t* n_ref, int64_t* n_peaks,
                         uint8_t* peaks, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- code clustering: k-means on the compact code -----------------------------------------------------
+ * Do the frames fall into a few hundred discrete units?  The two halves of a Lloyd iteration over a compact code vals /
+ * idx [n_rows, k] (1 <= k <= WSAE_CLUSTER_MAX_K) and 1 <= n_clusters <= WSAE_CLUSTER_MAX centroids; neither the dense
+ * [n_rows, hidden] code nor a [n_rows, n_clusters] product exists.  Ctx-free; the caller's stream, no allocation, no host
+ * synchronisation, no float atomics; argument errors are found on the host before any HIP call; n_rows == 0 returns
+ * WSAE_OK and touches nothing; every *_workspace_bytes returns -1 for invalid arguments (and 0 otherwise: neither call
+ * keeps anything); workspace contents are arbitrary on entry.  Activity, padding (seg[r] < 0; NULL: none) and col_of /
+ * n_cols are those of wsae_probe_plan (above).
+ *
+ * wsae_cluster_assign.  Ct fp32 [n_cols, ldc] (ldc >= n_clusters): the centroids TRANSPOSED - the row of a column holds
+ * its weight in every cluster, the layout of the probe's W.  bias fp32 [n_clusters] (nullable = 0).  On a row that is not
+ * padding and has at least one first-active entry with a column
+ *   score[c] = bias[c], then + v_j Ct[col_j][c] over those entries in ascending entry position; every step is an fp32
+ *              multiply and then an fp32 add (NOT fused);
+ *   a        = the lowest c at the maximum score, best = score[a];
+ *   second   = score[a2], a2 the lowest c != a at the maximum over c != a; -inf when n_clusters == 1;
+ *   n        = ONE chain of fp64 additions from 0 of double(v_j)^2 over the same entries in the same order;
+ *   inv_norm = float(1.0 / sqrt(n)): one fp64 root, one fp64 quotient, one rounding;
+ *   b        = best inv_norm (one fp32 product) with normalize != 0, which needs bias == NULL (WSAE_ERR_INVALID
+ *              otherwise); b = best without.
+ * Finite Ct and bias are the caller's duty.  Outputs, each nullable and skipped when NULL: assign int32 [n_rows] = a, and
+ * -1 on a padding row and on a row without such an entry (an EMPTY row); best, second, inv_norm fp32 [n_rows], exact
+ * zeros where assign is -1.  State, each nullable and skipped when NULL, integer sums on caller-owned device memory:
+ * count int64 [n_clusters] += 1 at a; best_q int64 [n_clusters] += llrintf(fminf(fmaxf(b, -4096), 4096) 2^20) at a;
+ * contingency int64 [n_clusters, n_classes] += 1 at [a][labels[r]] where the label lies in [0, n_classes) (labels int32
+ * [n_rows], nullable; with labels 1 <= n_classes <= WSAE_CLUSTER_MAX, and a contingency table needs labels); totals int64
+ * [3] += the assigned rows, the empty rows, the assigned rows with a label in range.  What is written for a row depends
+ * on that row alone; the sums are identical for any batching and any call order, and two shards add.  Cosine (spherical)
+ * k-means: unit centroids, normalize = 1, no bias.  Euclidean k-means: bias[c] = -|c|^2 / 2, since argmin |x - c|^2 is the
+ * argmax of this score.
+ *
+ * wsae_cluster_accumulate.  col_ptr / t_row / t_val / cap / n_cols: the plan wsae_probe_plan made of this very code, seg
+ * and col_of.  assign int32 [n_rows]; row_weight fp32 [n_rows] (nullable; for cosine the inv_norm of the assign call);
+ * S_q int64 [n_cols, lds] (lds >= n_clusters), the orientation of Ct.  Entry i of column p (the lists clipped to cap),
+ * with r = t_row[i] and x = t_val[i], or the one fp32 product t_val[i] row_weight[r], adds
+ * llrintf(fminf(x, 4096) 2^20) to S_q[p][assign[r]]; nothing where r is outside [0, n_rows), assign[r] is outside
+ * [0, n_clusters) or x is not > 0 (NaN is not).  Integer sums: bit-identical for any launch geometry, any batching and
+ * any call order; the states of two shards add.  The centroid of cluster c is S_q[.][c] / (count[c] 2^20). */
+#define WSAE_CLUSTER_MAX_K 128
+#define WSAE_CLUSTER_MAX 1024
+int64_t wsae_cluster_assign_workspace_bytes(int64_t n_rows, int32_t k, int32_t hidden, int32_t n_cols, int32_t n_clusters);
+int wsae_cluster_assign(const float* vals, const int32_t* idx, int32_t k, int32_t hidden, const int32_t* seg, int64_t n_rows,
+                        const int32_t* col_of, int32_t n_cols, const float* Ct, int64_t ldc, const float* bias,
+                        int32_t n_clusters, int32_t normalize, const int32_t* labels, int32_t n_classes, int32_t* assign,
+                        float* best, float* second, float* inv_norm, int64_t* count, int64_t* best_q, int64_t* contingency,
+                        int64_t* totals, void* workspace, int64_t workspace_bytes, void* stream);
+int64_t wsae_cluster_accumulate_workspace_bytes(int64_t n_rows, int32_t n_cols, int32_t n_clusters, int64_t cap);
+int wsae_cluster_accumulate(const int64_t* col_ptr, const int32_t* t_row, const float* t_val, int64_t cap, int32_t n_cols,
+                            const int32_t* assign, const float* row_weight, int64_t n_rows, int32_t n_clusters, int64_t* S_q,
+                            int64_t lds, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,9 +8,12 @@ threshold and lag), and sparse linear probes (softmax regression of a label on t
 the features, and the k-sparse probing curve), and sparse ridge regression (the Gram matrix of the code and the target
 moments in one streaming pass, then ridge fits of any feature subset as host-side solves), and code dynamics (the
 similarity of a frame's whole code to the code a few frames later, its statistics within and across labels, and the score
-of the curve's peaks against reference boundaries at every threshold).  Mirrors the names of the reference's ``whisper_sae.analysis.feature_viz``
+of the curve's peaks against reference boundaries at every threshold), and code clustering (k-means of the frames by
+their whole code, the units' purity, PNMI and adjusted Rand index against a label, and the unit strings).  Mirrors the names of the reference's ``whisper_sae.analysis.feature_viz``
 that sit on that path."""
 
+from .clustering import (ClusterScores, CodeKMeans, IterationStats, cluster_scores, collect_code_clusters,
+                         unit_sequences)
 from .coactivation import (CoactivationNeighbors, CoactivationTracker, collect_coactivation,
                            compare_activations)
 from .dictionary import NearestFeatures, compare_dictionaries, duplicate_features, nearest_features
@@ -43,4 +46,5 @@ __all__ = ["FeatureActivation", "TopKTracker", "collect_top_activations", "Neare
            "collect_probe_data", "sparse_probe_curve", "utterance_split", "RegressionCurve", "RegressionFit", "RegressionReport",
            "SparseRegression", "collect_regression", "regression_curve", "ridge_from_statistics", "top_correlated_features",
            "BoundaryCurve", "BoundaryScorer", "CodeDynamics", "DynamicsSummary", "LagStats", "boundaries_from_labels",
-           "boundary_curve", "collect_code_dynamics", "detect_boundaries", "frame_similarity", "novelty"]
+           "boundary_curve", "collect_code_dynamics", "detect_boundaries", "frame_similarity", "novelty", "ClusterScores", "CodeKMeans",
+           "IterationStats", "cluster_scores", "collect_code_clusters", "unit_sequences"]
