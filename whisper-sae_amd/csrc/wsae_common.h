@@ -269,6 +269,27 @@ __device__ __forceinline__ void nt_store4(float4* p, const float4& a) {
     __builtin_nontemporal_store(v, (f32x4*)p);
 }
 
+// 16-byte buffer store with a cache policy.  The aux operand's bits on gfx950:
+#define WSAE_AUX_PLAIN 0
+#define WSAE_AUX_NT 2      // non-temporal: the line stays (dirty) in the XCD's L2 like a plain store's
+#define WSAE_AUX_WT 16     // write-through (sc1): the bytes go on to memory at once and the line leaves the L2
+#define WSAE_AUX_WT_NT 18  // both
+// Rules of use: only on 16-byte-per-lane stores whose wave instruction writes whole 64-byte pieces; never on bytes the
+// same launch reads again or on a word of a ticket / hand-off.  Buffer offsets are 32 bits: wt_fits() says whether a
+// buffer of `bytes` can be addressed this way, the caller keeps the plain store where it cannot.  A compiler-visible
+// builtin, so the vmcnt waits in front of the arrival tickets go on covering these stores.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t wt_rsrc(const void* base) {
+    return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, 0x7fffffff, 0x00020000);
+}
+// (the resource's range check covers 0x7fffffff bytes and DROPS a store that crosses its end without a sound: the last
+// 16-byte store of a buffer that fits ends at or below that)
+__device__ __forceinline__ bool wt_fits(int64_t bytes) { return bytes <= 0x7fffffffll; }
+template <int AUX = WSAE_AUX_WT>
+__device__ __forceinline__ void wt_store4(const __amdgpu_buffer_rsrc_t& r, int64_t byte_off, const float4& a) {
+    typedef int i32x4_t __attribute__((ext_vector_type(4)));
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4_t, a), r, (int)byte_off, 0, AUX);
+}
+
 template <int DT>
 __device__ __forceinline__ float load_act(const void* p, int64_t i) {
     if (DT == WSAE_DT_BF16) return (float)((const bf16_t*)p)[i];

@@ -257,6 +257,25 @@ __device__ __forceinline__ void row_load(RowRegs<NI>& r, const float* __restrict
     }
 }
 
+// The p / m / v stores of a row: write-through where the pack fits 32-bit buffer offsets (wsae_common.h, wt_store4) - none of
+// these bytes is read again in the launch (the last block re-reads only the b_d / b_pre words, which stay plain).
+// EXTRA=-DWSAE_WT_UPDATE_ROWS=0 builds the plain form for an A/B.
+#ifndef WSAE_WT_UPDATE_ROWS
+#define WSAE_WT_UPDATE_ROWS 1
+#endif
+struct RowOut {
+    float *P, *M, *V;
+    __amdgpu_buffer_rsrc_t rP, rM, rV;
+    bool wt;
+};
+__device__ __forceinline__ void row_store(const RowOut& w, int64_t o, const float4& p, const float4& m, const float4& v) {
+    if (WSAE_WT_UPDATE_ROWS && w.wt) {
+        wt_store4(w.rP, o * 4, p); wt_store4(w.rM, o * 4, m); wt_store4(w.rV, o * 4, v);
+    } else {
+        *(float4*)(w.P + o) = p; *(float4*)(w.M + o) = m; *(float4*)(w.V + o) = v;
+    }
+}
+
 template <int NI>
 __device__ __forceinline__ void row_adam(RowRegs<NI>& r, const AdamArgs& a, float gs) {
 #pragma unroll
@@ -288,6 +307,7 @@ update_rows_kernel(float* __restrict__ P, const float* __restrict__ G, float* __
     const int hc = min(h, H - 1);
     constexpr bool BOTH = NI <= 3;  // both rows fit in registers at once (8 NI float4 per lane)
 
+    const RowOut wout = {P, M, V, wt_rsrc(P), wt_rsrc(M), wt_rsrc(V), wt_fits((max(oWe, oWd) + (int64_t)H * D) * 4)};
     RowRegs<NI> re, rd;
     row_load<NI>(re, P, G, M, V, oWe + (int64_t)hc * D, D, lane);
     if (BOTH) row_load<NI>(rd, P, G, M, V, oWd + (int64_t)hc * D, D, lane);
@@ -333,7 +353,7 @@ update_rows_kernel(float* __restrict__ P, const float* __restrict__ G, float* __
             const int d = lane * 4 + 256 * i;
             if (d < D) {
                 const int64_t o = oWe + (int64_t)h * D + d;
-                *(float4*)(P + o) = re.p[i]; *(float4*)(M + o) = re.m[i]; *(float4*)(V + o) = re.v[i];
+                row_store(wout, o, re.p[i], re.m[i], re.v[i]);
                 if (SHADOW) {
                     bf16x4 e;
                     e[0] = (bf16_t)re.p[i].x; e[1] = (bf16_t)re.p[i].y; e[2] = (bf16_t)re.p[i].z; e[3] = (bf16_t)re.p[i].w;
@@ -375,7 +395,7 @@ update_rows_kernel(float* __restrict__ P, const float* __restrict__ G, float* __
                 const int64_t o = oWd + (int64_t)h * D + d;
                 float4 p = rd.p[i];
                 p.x *= inv; p.y *= inv; p.z *= inv; p.w *= inv;
-                *(float4*)(P + o) = p; *(float4*)(M + o) = rd.m[i]; *(float4*)(V + o) = rd.v[i];
+                row_store(wout, o, p, rd.m[i], rd.v[i]);
                 if (SHADOW) {
                     bf16x4 o16;
                     o16[0] = (bf16_t)p.x; o16[1] = (bf16_t)p.y; o16[2] = (bf16_t)p.z; o16[3] = (bf16_t)p.w;

@@ -411,6 +411,10 @@ wgrad_kernel(const uint32_t* __restrict__ ent_pos, const T* __restrict__ ent_hid
 // different 64-byte halves of it (bit 2 of the slot), so the transposed reads are conflict-free.
 __device__ __forceinline__ int rm_swz(int r) { return (((r >> 1) & 1) << 2) | ((r >> 2) & 3); }
 
+// EXTRA=-DWSAE_WT_W2_SLABS=0 builds the epilogue's interior slab stores plain (A/B of the write-through form, wsae_common.h)
+#ifndef WSAE_WT_W2_SLABS
+#define WSAE_WT_W2_SLABS 1
+#endif
 // The tail of wgrad2_kernel and wgrad2s_kernel: a workgroup's 192 x 384 accumulator tile into its split-K slab, and the db_e row sums.
 __device__ __forceinline__ void w2_epilogue(char* smem, const f32x16 (&acc)[W2_MI][3], const f32x4& rs0, const f32x4& rs1,
                                             float* __restrict__ out, float* __restrict__ dbe_slab, int which, int split, int f0, int d0,
@@ -427,6 +431,10 @@ __device__ __forceinline__ void w2_epilogue(char* smem, const f32x16 (&acc)[W2_M
         constexpr int PSW = 100;  // floats per patch row: 96 + 4 (16-byte aligned rows, conflict-free column writes)
         float* patch = (float*)smem + wave * 32 * PSW;
         float* drow = dst + (int64_t)(f0 + wm * 32 * W2_MI) * rstr + d0 + wn * 96;
+        // (write-through where the slabs fit 32-bit buffer offsets: grad_finish reads them once, in another launch)
+        const __amdgpu_buffer_rsrc_t r_out = wt_rsrc(out);
+        const bool wt = WSAE_WT_W2_SLABS && wt_fits((int64_t)(dec_row_base + H) * rstr * 4);
+        const int64_t drow_off = drow - out;
 #pragma unroll
         for (int mi = 0; mi < W2_MI; ++mi) {
 #pragma unroll
@@ -440,7 +448,8 @@ __device__ __forceinline__ void w2_epilogue(char* smem, const f32x16 (&acc)[W2_M
                 const int idx = lane + 64 * i;      // float4 number inside the 32 x 96 patch
                 const int row = idx / 24, c4 = idx - row * 24;
                 const float4 v = *(const float4*)(patch + row * PSW + c4 * 4);
-                *(float4*)(drow + (int64_t)(mi * 32 + row) * rstr + c4 * 4) = v;
+                if (wt) wt_store4(r_out, (drow_off + (int64_t)(mi * 32 + row) * rstr + c4 * 4) * 4, v);
+                else *(float4*)(drow + (int64_t)(mi * 32 + row) * rstr + c4 * 4) = v;
             }
             __builtin_amdgcn_wave_barrier();
         }
@@ -985,14 +994,20 @@ __device__ __forceinline__ float wire_metric_digit(const float* __restrict__ m, 
     return (float)(((unsigned long long)q >> (4 * (i - 10))) & 15ull);
 }
 
+// The fp32 pack leaves write-through where it fits 32-bit buffer offsets (`wt`; wsae_common.h, wt_store4): the optimizer
+// launch behind reads it once.  The bf16 wire's 8-byte stores stay plain.  EXTRA=-DWSAE_WT_GRAD_FINISH=0 builds the plain form.
+#ifndef WSAE_WT_GRAD_FINISH
+#define WSAE_WT_GRAD_FINISH 1
+#endif
 template <typename OT>
-__device__ __forceinline__ void gf_store4(OT* p, const float4& a) {
+__device__ __forceinline__ void gf_store4(OT* out, const __amdgpu_buffer_rsrc_t& r, bool wt, int64_t i, const float4& a) {
     if constexpr (sizeof(OT) == 2) {
         bf16x4 o;
         o[0] = (bf16_t)a.x; o[1] = (bf16_t)a.y; o[2] = (bf16_t)a.z; o[3] = (bf16_t)a.w;
-        *(bf16x4*)p = o;
+        *(bf16x4*)(out + i) = o;
     } else {
-        *(float4*)p = a;
+        if (WSAE_WT_GRAD_FINISH && wt) wt_store4(r, i * 4, a);
+        else *(float4*)(out + i) = a;
     }
 }
 
@@ -1023,6 +1038,8 @@ grad_finish_kernel(const float* __restrict__ slabs, const float* __restrict__ db
         const int lane = tid & 63, wave = tid >> 6;
         const int nc = D >> 2;  // float4 chunks per row
         const int rpw = (nrows + nrb * 4 - 1) / (nrb * 4);
+        const __amdgpu_buffer_rsrc_t r_out = wt_rsrc(out);
+        const bool wt = wt_fits((max(o.oWe, o.oWd) + (int64_t)H * D) * (int64_t)sizeof(OT));
         float sq = 0.f;  // sum of squares of everything this block writes (global-norm partial)
         for (int q = 0; q < rpw; q += 2) {
             const int r0 = row0 + (bid * 4 + wave) * rpw + q;
@@ -1049,11 +1066,11 @@ grad_finish_kernel(const float* __restrict__ slabs, const float* __restrict__ db
             }
             const int total = nr * nc;
             const float4* base = (const float4*)slabs + (int64_t)(r0 - slab_row0) * NS * nc;  // [row][slot][D]
-            OT* orow[2];
+            int64_t orow[2];  // element offsets into out
 #pragma unroll
             for (int j2 = 0; j2 < 2; ++j2) {
                 const int r = r0 + j2;
-                orow[j2] = out + (r < H ? o.oWe + (int64_t)r * D : o.oWd + (int64_t)(r - H) * D);
+                orow[j2] = r < H ? o.oWe + (int64_t)r * D : o.oWd + (int64_t)(r - H) * D;
             }
             for (int c0 = 0; c0 < total; c0 += 64 * TR) {
                 float4 v[TR][NS];
@@ -1088,7 +1105,7 @@ grad_finish_kernel(const float* __restrict__ slabs, const float* __restrict__ db
                         const float b1 = j ? be[1] : be[0];
                         a.x -= b1 * bp.x; a.y -= b1 * bp.y; a.z -= b1 * bp.z; a.w -= b1 * bp.w;
                     }
-                    gf_store4<OT>((j ? orow[1] : orow[0]) + 4 * c, a);
+                    gf_store4<OT>(out, r_out, wt, (j ? orow[1] : orow[0]) + 4 * c, a);
                     sq += a.x * a.x + a.y * a.y + a.z * a.z + a.w * a.w;
                 }
             }
