@@ -996,6 +996,67 @@ int wsae_cluster_accumulate(const int64_t* col_ptr, const int32_t* t_row, const 
                             const int32_t* assign, const float* row_weight, int64_t n_rows, int32_t n_clusters, int64_t* S_q,
                             int64_t lds, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- ABX phone discrimination: DTW distances between segments and the triple count --------------------
+ * Is a token X of a phone closer to another token A of the same phone than to a token B of another one?  "Closer" is the
+ * DTW-aligned frame distance between two row ranges of a compact code vals / idx [n_rows, k] (1 <= k <= WSAE_DTW_MAX_K).
+ * Ctx-free; the caller's stream, no allocation, no host synchronisation, no float atomics; argument errors are found on
+ * the host before any HIP call; every *_workspace_bytes returns -1 for invalid arguments; workspace contents are
+ * arbitrary on entry.
+ *
+ * wsae_dtw_matrix.  Activity, padding (seg[r] < 0; seg nullable), weight, u = v weight[f] and the per-row quantities n_r
+ * and a_r are exactly those of wsae_dyn_update (above): an index repeated within a row counts once, with the value of its
+ * first active entry.  Items are row ranges [start, start + len) of this one code; a_start / a_len int32 [n_a] and
+ * b_start / b_len int32 [n_b] in DEVICE memory.  An item is valid iff 1 <= len <= WSAE_DTW_MAX_LEN, start >= 0 and
+ * start + len <= n_rows; items may overlap and repeat.  For frame r of an a-item and frame q of a b-item - any two rows,
+ * there is no same-segment condition - with p the entry positions 0 .. k - 1 of row q (the B frame) in ascending order,
+ * restricted to the positions that hold an active feature of q which is active on r as well:
+ *   s = ONE chain of fp64 additions from 0 of double(u_q(f_p)) double(u_r(f_p)) over those p; i = their number.
+ * WSAE_DTW_COSINE: c = 0 where n_r == 0 or n_q == 0, else c = s / sqrt(n_r n_q) in fp64 (one product, one square root, one
+ * quotient) and 1 unless c <= 1.  WSAE_DTW_JACCARD: c = 0 where a_r + a_q - i == 0, else the fp64 quotient
+ * i / (a_r + a_q - i); it needs presence, not values (a u that underflowed to 0 counts).  The frame cost is
+ * e = float(1.0 - c): one fp64 subtraction, one rounding.
+ * The dynamic program of an a-item of n frames and a b-item of m frames: D[0][0] = double(e[0][0]), L[0][0] = 1; every
+ * other cell takes the predecessor with the smallest D among those that exist, (i-1, j-1), (i-1, j), (i, j-1), ties to
+ * the earlier one in that order; D[i][j] = double(e[i][j]) + D[pred] (one fp64 addition), L[i][j] = L[pred] + 1.
+ *   dist fp32 [n_a, ldd] (ldd >= n_b): float(D[n-1][m-1] / double(L[n-1][m-1])) with normalize != 0 (the path-length
+ *   normalisation of the ABX literature), float(D[n-1][m-1]) without; steps int32 [n_a, ldd] (nullable): L[n-1][m-1].
+ *   A pair with an invalid item gets NaN and 0.  Every cell [a][b < n_b] is written and nothing beyond column n_b of a row.
+ * A sequential loop reproduces every bit.  A cell depends on its two items alone: not on the launch geometry, not on the
+ * other items of the call, not on how the item lists are split into calls.  n_a == 0, n_b == 0 or n_rows == 0 returns
+ * WSAE_OK and touches nothing.  An active value of +inf, or a u that overflows, is the caller's duty to avoid: distances
+ * of items that hold one are unspecified.  Workspace (8-byte aligned): wsae_dtw_workspace_bytes - that of
+ * wsae_dyn_update, the canonical code of all n_rows.
+ *
+ * wsae_abx_count.  dist fp32 [n_x, ldd] holds rows x_lo .. x_lo + n_x - 1 of an items x items distance matrix (ldd >=
+ * n_items, x_lo >= 0, x_lo + n_x <= n_items); cat, ctx, spk int32 [n_items] in device memory.  ctx is nullable (= one
+ * context); spk is nullable only with WSAE_ABX_ANY, which ignores it.  An item takes part iff cat lies in [0, n_cats)
+ * (1 <= n_cats <= WSAE_ABX_MAX_CATS), ctx >= 0 where ctx is given and spk >= 0 where the mode reads it.  An ordered
+ * triple (a, b, x) of three distinct items that take part, x in the window, is admissible iff cat[a] == cat[x] != cat[b],
+ * ctx[a] == ctx[b] == ctx[x], and under WSAE_ABX_WITHIN spk[a] == spk[b] == spk[x], under WSAE_ABX_ACROSS
+ * spk[a] == spk[b] != spk[x].  An admissible triple whose dist[x][a] or dist[x][b] is NaN adds 1 to skipped[0].  Any
+ * other adds 1 to total[cat[x]][cat[b]] and, to wins2[cat[x]][cat[b]], 2 where dist[x][a] < dist[x][b] and 1 where they
+ * are equal.  wins2, total int64 [n_cats, n_cats] and skipped int64 [1]: caller-owned, zero-initialised device memory.
+ * All sums are integers: windows, shards and call orders add, whatever the launch geometry.  n_x == 0 returns WSAE_OK and
+ * touches nothing.  Workspace (8-byte aligned): wsae_abx_workspace_bytes - 4 bytes per (x, item): the a-candidates of a
+ * row. */
+#define WSAE_DTW_MAX_LEN 64
+#define WSAE_DTW_MAX_K 128
+#define WSAE_DTW_COSINE 0
+#define WSAE_DTW_JACCARD 2 /* the numbering of WSAE_DYN_* */
+#define WSAE_ABX_ANY 0
+#define WSAE_ABX_WITHIN 1
+#define WSAE_ABX_ACROSS 2
+#define WSAE_ABX_MAX_CATS 1024
+int64_t wsae_dtw_workspace_bytes(int64_t n_rows, int32_t k, int32_t hidden, int32_t n_a, int32_t n_b);
+int wsae_dtw_matrix(const float* vals, const int32_t* idx, int32_t k, int32_t hidden, const int32_t* seg, const float* weight,
+                    int64_t n_rows, const int32_t* a_start, const int32_t* a_len, int32_t n_a, const int32_t* b_start,
+                    const int32_t* b_len, int32_t n_b, int32_t metric, int32_t normalize, float* dist, int32_t* steps,
+                    int64_t ldd, void* workspace, int64_t workspace_bytes, void* stream);
+int64_t wsae_abx_workspace_bytes(int32_t n_items, int32_t n_x, int32_t n_cats);
+int wsae_abx_count(const float* dist, int64_t ldd, int32_t x_lo, int32_t n_x, int32_t n_items, const int32_t* cat,
+                   const int32_t* ctx, const int32_t* spk, int32_t n_cats, int32_t mode, int64_t* wins2, int64_t* total,
+                   int64_t* skipped, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,8 @@
 // Code dynamics: how the code of a frame as a whole moves through time.
 //
 // wsae_dyn_update: the similarity (cosine, dot, Jaccard) of the codes of rows r and r + lag for up to 16 lags, as a
-// [rows, lags] matrix and / or as integer statistics per (lag, label class).  Two launches.  dyn_canon_kernel, one wave
+// [rows, lags] matrix and / or as integer statistics per (lag, label class).  Two launches.  dyn_canon_kernel
+// (wsae_dyn_canon.h, shared with wsae_abx.hip), one wave
 // per row on the front end of wsae_codewalk.h (one lane per entry, two for k > 64, the first active entry of a feature
 // wins), writes the canonical code into the workspace: per entry u = v weight[f] and f, or -1 where the entry is not
 // active, per row the norm and the number of active features.  dyn_sim_kernel, one wave per row r, keeps the canonical
@@ -20,105 +21,12 @@
 // mask of row ages plus one bit for their kind.  An item of the other kind hits the oldest of them.
 #include <math.h>
 
-#include "wsae_codewalk.h"
+#include "wsae_dyn_canon.h"
 
 namespace {
 
-constexpr int DY_BLOCK = 256;        // four waves, one row each per pass
-constexpr int DY_MAX_BLOCKS = 4096;  // more rows than DY_MAX_BLOCKS * 4: the grid-stride loop
 constexpr int DY_CLASSES = 3;
 constexpr int DY_CELLS = WSAE_DYN_MAX_LAGS * DY_CLASSES;
-
-struct DynArgs {
-    const float* vals;
-    const int32_t* idx;
-    const int32_t* seg;     // nullable
-    const float* weight;    // nullable
-    const int32_t* label;   // nullable
-    int64_t n_rows;
-    int k, hidden, L, metric;
-    int lag[WSAE_DYN_MAX_LAGS];
-    float* cu;      // [n_rows, k] canonical values (0 where inactive)
-    int32_t* cf;    // [n_rows, k] canonical features (-1 where inactive)
-    double* nrm;    // [n_rows]
-    int32_t* act;   // [n_rows]
-    float* sim;     // [n_rows, L], nullable
-    unsigned long long* pairs;  // the state, nullable as a whole
-    unsigned long long* sim_q;
-    unsigned long long* sq_q;
-    unsigned long long* hist;
-    unsigned long long* total_rows;
-};
-
-__device__ __forceinline__ float lane_f32(float x, int lane) {
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), lane));
-}
-
-__global__ __launch_bounds__(DY_BLOCK) void dyn_canon_kernel(DynArgs a) {
-    const int lane = threadIdx.x & 63;
-    const int64_t wave = (int64_t)blockIdx.x * (DY_BLOCK / 64) + (threadIdx.x >> 6);
-    const int64_t n_waves = (int64_t)gridDim.x * (DY_BLOCK / 64);
-    const int k = a.k, k0 = k < 64 ? k : 64;
-    for (int64_t r = wave; r < a.n_rows; r += n_waves) {
-        float v0, v1;
-        int f0, f1, c0, c1;
-        probe_load_row(a.vals, a.idx, k, r, lane, v0, f0, v1, f1);
-        probe_row_columns(v0, f0, v1, f1, k, a.hidden, nullptr, lane, c0, c1);
-        if (a.seg != nullptr && a.seg[r] < 0) c0 = -1, c1 = -1;  // (padding: nothing is active)
-        float u0 = 0.f, u1 = 0.f;
-        if (c0 >= 0) {
-            u0 = v0;
-            if (a.weight != nullptr) {
-                const float w = a.weight[c0];
-                u0 = v0 * w;
-                if (!(w > 0.f)) c0 = -1, u0 = 0.f;
-            }
-        }
-        if (c1 >= 0) {
-            u1 = v1;
-            if (a.weight != nullptr) {
-                const float w = a.weight[c1];
-                u1 = v1 * w;
-                if (!(w > 0.f)) c1 = -1, u1 = 0.f;
-            }
-        }
-        double n = 0.0;  // one chain in ascending entry position, the same in every lane
-        for (int d = 0; d < k0; ++d) {
-            const double x = (double)lane_f32(u0, d);
-            if (__builtin_amdgcn_readlane(c0, d) >= 0) n += x * x;
-        }
-        for (int d = 64; d < k; ++d) {
-            const double x = (double)lane_f32(u1, d - 64);
-            if (__builtin_amdgcn_readlane(c1, d - 64) >= 0) n += x * x;
-        }
-        const int active = __popcll(__ballot(c0 >= 0)) + __popcll(__ballot(c1 >= 0));
-        if (lane < k) {
-            a.cu[r * k + lane] = u0;
-            a.cf[r * k + lane] = c0;
-        }
-        if (lane + 64 < k) {
-            a.cu[r * k + lane + 64] = u1;
-            a.cf[r * k + lane + 64] = c1;
-        }
-        if (lane == 0) {
-            a.nrm[r] = n;
-            a.act[r] = active;
-        }
-    }
-}
-
-// the canonical entries lane and lane + 64 of row r (f = -1 beyond k)
-__device__ __forceinline__ void dyn_load_canon(const DynArgs& a, int64_t r, int lane, float& u0, int& f0, float& u1, int& f1) {
-    u0 = 0.f, u1 = 0.f, f0 = -1, f1 = -1;
-    if (lane < a.k) {
-        u0 = a.cu[r * a.k + lane];
-        f0 = a.cf[r * a.k + lane];
-    }
-    if (lane + 64 < a.k) {
-        u1 = a.cu[r * a.k + lane + 64];
-        f1 = a.cf[r * a.k + lane + 64];
-    }
-}
 
 // One step of the chain: the entry (f, u) of row r, f >= 0 and the same in every lane, against the lanes of row q.
 __device__ __forceinline__ void dyn_match(int f, float u, float qu0, int qf0, float qu1, int qf1, bool wide, double& s,
@@ -240,20 +148,6 @@ __global__ __launch_bounds__(DY_BLOCK) void dyn_sim_kernel(DynArgs a) {
 inline bool dyn_args_ok(int64_t n_rows, int k, int hidden, int n_lags) {
     return n_rows >= 0 && n_rows <= INT_MAX && k >= 1 && k <= WSAE_DYN_MAX_K && hidden >= 1 && n_lags >= 1 &&
            n_lags <= WSAE_DYN_MAX_LAGS;
-}
-
-// the sections of the workspace of wsae_dyn_update: cu, cf, nrm, act
-struct DynLayout {
-    int64_t cu, cf, nrm, act, total;
-};
-inline DynLayout dyn_layout(int64_t n_rows, int k) {
-    DynLayout w;
-    w.cu = 0;
-    w.cf = w.cu + align256(4 * n_rows * k);
-    w.nrm = w.cf + align256(4 * n_rows * k);
-    w.act = w.nrm + align256(8 * n_rows);
-    w.total = w.act + align256(4 * n_rows);
-    return w;
 }
 
 // ---- boundary scoring ------------------------------------------------------------------------------------------------------
@@ -418,8 +312,7 @@ extern "C" int wsae_dyn_update(const float* vals, const int32_t* idx, int32_t k,
     a.sim = sim;
     a.pairs = (unsigned long long*)pairs, a.sim_q = (unsigned long long*)sim_q, a.sq_q = (unsigned long long*)sq_q;
     a.hist = (unsigned long long*)hist, a.total_rows = (unsigned long long*)total_rows;
-    const int64_t blocks = ceil_div64(n_rows, DY_BLOCK / 64);
-    const int grid = (int)(blocks < DY_MAX_BLOCKS ? blocks : DY_MAX_BLOCKS);
+    const int grid = dyn_canon_grid(n_rows);
     dyn_canon_kernel<<<grid, DY_BLOCK, 0, (hipStream_t)stream>>>(a);
     WSAE_LAUNCH_CHECK();
     dyn_sim_kernel<<<grid, DY_BLOCK, 0, (hipStream_t)stream>>>(a);

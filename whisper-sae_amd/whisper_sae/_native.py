@@ -32,6 +32,8 @@ DYN_COSINE, DYN_DOT, DYN_JACCARD = 0, 1, 2  # wsae_dyn_update
 DYN_MAX_K, DYN_MAX_LAGS, DYN_MAX_LAG, DYN_BINS = 128, 16, 1024, 64
 BOUNDARY_MAX_THR, BOUNDARY_MAX_TOL = 256, 64  # wsae_boundary_score
 CLUSTER_MAX_K, CLUSTER_MAX = 128, 1024  # wsae_cluster_assign / wsae_cluster_accumulate
+DTW_MAX_LEN, DTW_MAX_K, DTW_COSINE, DTW_JACCARD = 64, 128, 0, 2  # wsae_dtw_matrix
+ABX_ANY, ABX_WITHIN, ABX_ACROSS, ABX_MAX_CATS = 0, 1, 2, 1024  # wsae_abx_count
 BTK_STATE_WORDS = 8  # wsae_batch_topk_state: threshold, beta, last_t (f32), saturated_rows, kept, 3 reserved (i32)
 
 
@@ -163,6 +165,11 @@ SIGNATURES = {
                                       _p, _p, _p, _p, _p, _i64, _p]),
     "wsae_cluster_accumulate_workspace_bytes": (_i64, [_i64, _i32, _i32, _i64]),
     "wsae_cluster_accumulate": (C.c_int, [_p, _p, _p, _i64, _i32, _p, _p, _i64, _i32, _p, _i64, _p, _i64, _p]),
+    "wsae_dtw_workspace_bytes": (_i64, [_i64, _i32, _i32, _i32, _i32]),
+    "wsae_dtw_matrix": (C.c_int, [_p, _p, _i32, _i32, _p, _p, _i64, _p, _p, _i32, _p, _p, _i32, _i32, _i32, _p, _p, _i64, _p, _i64,
+                                  _p]),
+    "wsae_abx_workspace_bytes": (_i64, [_i32, _i32, _i32]),
+    "wsae_abx_count": (C.c_int, [_p, _i64, _i32, _i32, _i32, _p, _p, _p, _i32, _i32, _p, _p, _p, _p, _i64, _p]),
     "wsae_relu_needs_hidden":(C.c_int, [_p, _i32]),
     "wsae_relu_forward": (C.c_int, [_p, _p, _p, _i32, _p, _i32, _f32, _p, _p, _p, _p, _p]),
     "wsae_relu_backward": (C.c_int, [_p, _p, _p, _i32, _p, _i32, _f32, _p, _p, _p, _p]),

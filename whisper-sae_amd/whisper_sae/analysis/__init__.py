@@ -9,7 +9,8 @@ the features, and the k-sparse probing curve), and sparse ridge regression (the 
 moments in one streaming pass, then ridge fits of any feature subset as host-side solves), and code dynamics (the
 similarity of a frame's whole code to the code a few frames later, its statistics within and across labels, and the score
 of the curve's peaks against reference boundaries at every threshold), and code clustering (k-means of the frames by
-their whole code, the units' purity, PNMI and adjusted Rand index against a label, and the unit strings).  Mirrors the names of the reference's ``whisper_sae.analysis.feature_viz``
+their whole code, the units' purity, PNMI and adjusted Rand index against a label, and the unit strings), and ABX phone discrimination (DTW distances between segments of the code and the count of the
+triples in which a token lies closer to a token of its own phone than to one of another).  Mirrors the names of the reference's ``whisper_sae.analysis.feature_viz``
 that sit on that path."""
 
 from .clustering import (ClusterScores, CodeKMeans, IterationStats, cluster_scores, collect_code_clusters,
@@ -17,6 +18,7 @@ from .clustering import (ClusterScores, CodeKMeans, IterationStats, cluster_scor
 from .coactivation import (CoactivationNeighbors, CoactivationTracker, collect_coactivation,
                            compare_activations)
 from .dictionary import NearestFeatures, compare_dictionaries, duplicate_features, nearest_features
+from .discrimination import AbxItems, AbxScores, collect_abx, items_from_labels, segment_distances
 from .dynamics import (BoundaryCurve, BoundaryScorer, CodeDynamics, DynamicsSummary, LagStats, boundaries_from_labels,
                        boundary_curve, collect_code_dynamics, detect_boundaries, frame_similarity, novelty)
 from .feature_viz import FeatureActivation, TopKTracker, collect_top_activations
@@ -47,4 +49,5 @@ __all__ = ["FeatureActivation", "TopKTracker", "collect_top_activations", "Neare
            "SparseRegression", "collect_regression", "regression_curve", "ridge_from_statistics", "top_correlated_features",
            "BoundaryCurve", "BoundaryScorer", "CodeDynamics", "DynamicsSummary", "LagStats", "boundaries_from_labels",
            "boundary_curve", "collect_code_dynamics", "detect_boundaries", "frame_similarity", "novelty", "ClusterScores", "CodeKMeans",
-           "IterationStats", "cluster_scores", "collect_code_clusters", "unit_sequences"]
+           "IterationStats", "cluster_scores", "collect_code_clusters", "unit_sequences", "AbxItems", "AbxScores", "collect_abx",
+           "items_from_labels", "segment_distances"]
