@@ -1057,6 +1057,83 @@ int wsae_abx_count(const float* dist, int64_t ldd, int32_t x_lo, int32_t n_x, in
                    const int32_t* ctx, const int32_t* spk, int32_t n_cats, int32_t mode, int64_t* wins2, int64_t* total,
                    int64_t* skipped, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- token association: feature-by-token counts in a device hash table ------------------------------
+ * The sparse counterpart of the label association: exact integer statistics of every (feature, token) pair that occurs,
+ * for vocabularies of up to WSAE_PAIR_MAX_TOKENS tokens, in memory proportional to the number of distinct pairs, straight
+ * from a compact code vals / idx [n_rows, k] (1 <= k <= WSAE_PAIR_MAX_K) and tokens int32 [n_rows].  Ctx-free; the caller's
+ * stream, no allocation, no host synchronisation, no float atomics; argument errors are found on the host before any HIP
+ * call.
+ *
+ * Activity (the rule of wsae_label_update): feature f is active on row r iff the row is not padding (seg[r] >= 0, or seg
+ * == NULL) and some entry has idx == f, v > 0 and 0 <= f < hidden; an index repeated within a row counts once, with the
+ * value of its first active entry.  NaN is never active, +inf is.  Pairs: with the call's single lag (-1024 <= lag <=
+ * 1024) row r forms a pair iff it is not padding, 0 <= r + lag < n_rows, seg[r + lag] == seg[r] and 0 <= tokens[r + lag]
+ * < n_tokens (1 <= n_tokens <= WSAE_PAIR_MAX_TOKENS); its token is t = tokens[r + lag].  Any other token value (-1 = "no
+ * token") drops the pair and nothing else.  Lags never cross an utterance: a call sees whole utterances.
+ *
+ * State (caller-owned device memory).  The table: keys uint64 [cap], every slot initialised to 2^64 - 1 = empty; cnt
+ * int32 [cap] and sum_q int64 [cap], zero-initialised; cap a power of two, 2^10 <= cap <= 2^31.  The key of a pair is
+ * (uint64) f << 32 | t, which never reaches the empty marker.  status int64 [2], zero-initialised: {occupied slots,
+ * dropped contributions}.  The marginals, zero-initialised: feat_rows int64 [hidden], tok_rows int64 [n_tokens],
+ * pair_rows int64 [1].
+ *
+ * wsae_pair_update.  Per pair (r, t): pair_rows += 1, tok_rows[t] += 1, and for every feature f active on r with value v:
+ * feat_rows[f] += 1 and, in the table under the key of (f, t), cnt += 1 and sum_q += rint(min(v, 4096) 2^20) (the fixed
+ * point of wsae_profile_update).  Insertion: the first slot is h(key) & (cap - 1) with h the splitmix64 finaliser,
+ *     x ^= x >> 30;  x *= 0xBF58476D1CE4E5B9;  x ^= x >> 27;  x *= 0x94D049BB133111EB;  x ^= x >> 31
+ * in uint64 arithmetic; probing is linear with wrap-around; a probe reads the slot and, where it sees it empty, makes one
+ * 64-bit compare-and-swap (empty -> key); a slot that was empty or holds the key takes the two integer adds.  Every slot
+ * claimed adds 1 to status[0].  Nothing locks and nothing waits for another thread: the only loop is the probe loop, of at
+ * most cap probes; a contribution that finds no slot within them adds 1 to status[1] and is dropped (the marginals still
+ * count it).  The caller keeps status[0] before the call + n_rows k <= cap / 2: then nothing is ever dropped and probe
+ * sequences stay short.  Every field is an integer sum: the set of (key, cnt, sum_q) triples and the marginals do not
+ * depend on the launch geometry, on the order of the calls or on the grouping of whole utterances into calls; the slot a
+ * key lands in may vary from run to run, and nothing reads the layout.  0 <= n_rows <= 2^31 - 1 per call; n_rows == 0
+ * returns WSAE_OK and touches nothing.
+ *
+ * wsae_pair_merge.  Every slot of the source (src_keys / src_cnt / src_sum_q [src_cap], src_cap >= 1, any number - a
+ * table or a plain list) whose key is not empty is inserted into the destination table by the rule above, with its cnt
+ * and sum_q added; status is the destination's.  Serves growth (into an empty table of twice the size), the merge of two
+ * shards and loading; the marginals are plain vectors that the caller adds.  The caller keeps status[0] + the occupied
+ * slots of the source <= cap / 2.  The two tables must not be the same memory.
+ *
+ * wsae_pair_top.  by == WSAE_PAIR_BY_FEATURE: per feature (n_groups == hidden) over its tokens; by == WSAE_PAIR_BY_TOKEN:
+ * per token (n_groups == n_tokens) over its features.  ids int32 [n_groups, n], scores fp64 [n_groups, n], counts int32
+ * [n_groups, n], sums int64 [n_groups, n] (1 <= n <= WSAE_PAIR_MAX_N): per group the n pairs with the best score, sorted
+ * by score descending, then id ascending (the id is the token of a feature's list and the feature of a token's); pairs
+ * with cnt < min_count are skipped; the tail of a short list is (-1, -inf, 0, 0).  A key whose feature or token lies
+ * outside [0, hidden) x [0, n_tokens) is skipped.  Scores are fp64 from the integers in exactly this operation order,
+ * with c = cnt, a = feat_rows[f], b = tok_rows[t], N = pair_rows[0], each converted to double first:
+ *     WSAE_PAIR_COUNT c;  WSAE_PAIR_PRECISION c / a;  WSAE_PAIR_RECALL c / b;  WSAE_PAIR_F1 (2 c) / (a + b);
+ *     WSAE_PAIR_JACCARD c / ((a + b) - c);  WSAE_PAIR_LIFT (c N) / (a b);  WSAE_PAIR_MEAN ((double) sum_q 2^-20) / c
+ * IEEE multiplies, adds and divides only, so a host loop reproduces every bit (a pair whose score is NaN - marginals that
+ * do not belong to the table - is skipped).  The order is total, so the result does not depend on the slot layout.
+ * Workspace (8-byte aligned): wsae_pair_top_workspace_bytes - two uint32 vectors over the groups and one over the slots;
+ * -1 for invalid arguments; contents arbitrary on entry. */
+#define WSAE_PAIR_MAX_K 128
+#define WSAE_PAIR_MAX_TOKENS (1 << 24)
+#define WSAE_PAIR_MAX_N 32
+#define WSAE_PAIR_BY_FEATURE 0
+#define WSAE_PAIR_BY_TOKEN 1
+#define WSAE_PAIR_COUNT 0
+#define WSAE_PAIR_PRECISION 1
+#define WSAE_PAIR_RECALL 2
+#define WSAE_PAIR_F1 3
+#define WSAE_PAIR_JACCARD 4
+#define WSAE_PAIR_LIFT 5
+#define WSAE_PAIR_MEAN 6
+int wsae_pair_update(const float* vals, const int32_t* idx, int32_t k, int32_t hidden, const int32_t* seg,
+                     const int32_t* tokens, int64_t n_rows, int32_t n_tokens, int32_t lag, uint64_t* keys, int32_t* cnt,
+                     int64_t* sum_q, int64_t cap, int64_t* status, int64_t* feat_rows, int64_t* tok_rows, int64_t* pair_rows,
+                     void* stream);
+int wsae_pair_merge(const uint64_t* src_keys, const int32_t* src_cnt, const int64_t* src_sum_q, int64_t src_cap, uint64_t* keys,
+                    int32_t* cnt, int64_t* sum_q, int64_t cap, int64_t* status, void* stream);
+int64_t wsae_pair_top_workspace_bytes(int64_t cap, int32_t n_groups);
+int wsae_pair_top(const uint64_t* keys, const int32_t* cnt, const int64_t* sum_q, int64_t cap, const int64_t* feat_rows,
+                  const int64_t* tok_rows, const int64_t* pair_rows, int32_t hidden, int32_t n_tokens, int32_t by,
+                  int32_t n_groups, int32_t score, int32_t min_count, int32_t n, int32_t* ids, double* scores, int32_t* counts,
+                  int64_t* sums, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,7 +10,9 @@ moments in one streaming pass, then ridge fits of any feature subset as host-sid
 similarity of a frame's whole code to the code a few frames later, its statistics within and across labels, and the score
 of the curve's peaks against reference boundaries at every threshold), and code clustering (k-means of the frames by
 their whole code, the units' purity, PNMI and adjusted Rand index against a label, and the unit strings), and ABX phone discrimination (DTW distances between segments of the code and the count of the
-triples in which a token lies closer to a token of its own phone than to one of another).  Mirrors the names of the reference's ``whisper_sae.analysis.feature_viz``
+triples in which a token lies closer to a token of its own phone than to one of another), and token association (exact
+counts of every (feature, token) pair that occurs, for vocabularies of 10^4 to 10^7 tokens, in a device hash table, with the
+top tokens of a feature and the top features of a token ranked on the device).  Mirrors the names of the reference's ``whisper_sae.analysis.feature_viz``
 that sit on that path."""
 
 from .clustering import (ClusterScores, CodeKMeans, IterationStats, cluster_scores, collect_code_clusters,
@@ -33,6 +35,7 @@ from .profile import (ActivationProfile, ActivationSampler, DensityHistogram, Pr
 from .regression import (RegressionCurve, RegressionFit, RegressionReport, SparseRegression, collect_regression,
                          regression_curve, ridge_from_statistics, top_correlated_features)
 from .temporal import FeatureEvents, RunSummary, RunTracker, collect_runs, summarize_runs, top_temporal_features
+from .tokens import PairExport, TokenAssociation, TopPairs, collect_token_association
 from .triggered import (TriggeredAverageTracker, as_spectrogram, collect_triggered_averages, mel_frames,
                         top_template_features)
 
@@ -50,4 +53,4 @@ __all__ = ["FeatureActivation", "TopKTracker", "collect_top_activations", "Neare
            "BoundaryCurve", "BoundaryScorer", "CodeDynamics", "DynamicsSummary", "LagStats", "boundaries_from_labels",
            "boundary_curve", "collect_code_dynamics", "detect_boundaries", "frame_similarity", "novelty", "ClusterScores", "CodeKMeans",
            "IterationStats", "cluster_scores", "collect_code_clusters", "unit_sequences", "AbxItems", "AbxScores", "collect_abx",
-           "items_from_labels", "segment_distances"]
+           "items_from_labels", "segment_distances", "PairExport", "TokenAssociation", "TopPairs", "collect_token_association"]
