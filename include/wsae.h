@@ -1134,6 +1134,68 @@ int wsae_pair_top(const uint64_t* keys, const int32_t* cnt, const int64_t* sum_q
                   int32_t n_groups, int32_t score, int32_t min_count, int32_t n, int32_t* ids, double* scores, int32_t* counts,
                   int64_t* sums, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- token alignment: cross-attention cost and DTW to frame labels ---------------------------------
+ * Whisper's word-timestamp recipe as two kernels: the attention weights of a few alignment heads are z-scored over the
+ * token axis, median-filtered along time, averaged over the heads and negated (wsae_align_cost); dynamic time warping
+ * over that tokens x frames matrix gives every encoder frame the token row that owns it (wsae_align_dtw).  Ctx-free; the
+ * caller's stream, no allocation, no host synchronisation, no float atomics; argument errors are found on the host before
+ * any HIP call.  Every output of an utterance depends on that utterance alone: not on the launch geometry, not on the
+ * other utterances of the call.  A sequential loop reproduces every bit (tests/align_oracle.py).
+ *
+ * wsae_align_cost.  w [n_utt, n_heads, ld_t, ld_f] of w_dtype WSAE_DT_F32, WSAE_DT_BF16 or WSAE_DT_F16 (every value converts
+ * to double exactly); n_tok, n_frames int32 [n_utt] in DEVICE memory: the token rows and the encoder frames of utterance
+ * u that are read (Whisper's num_frames // 2 crop); width odd, 1 <= width <= WSAE_ALIGN_MAX_WIDTH, p = width / 2;
+ * 1 <= n_heads <= WSAE_ALIGN_MAX_HEADS.  An utterance is invalid iff n_tok < 1, n_tok > min(ld_t, WSAE_ALIGN_MAX_TOK),
+ * n_frames <= p, n_frames > min(ld_f, WSAE_ALIGN_MAX_FRAMES), or any w[u][h][i < n_tok][j < n_frames] is not finite.
+ * Nothing else of w is read.  For head h and frame j < n_frames:
+ *   mean = (ONE chain of fp64 additions from 0 of double(w[h][i][j]), i = 0 .. n_tok - 1) / double(n_tok);
+ *   var  = (ONE chain of fp64 additions from 0 of d d, d = double(w[h][i][j]) - mean: product, then add, no fused
+ *          multiply-add) / double(n_tok) - the population variance; sd = sqrt(var) in fp64;
+ *   z[h][i][j] = float((double(w[h][i][j]) - mean) / sd) + 0.0f (one rounding; never -0), and 0 where sd == 0;
+ *   m[h][i][j] = the median of z[h][i][q] over q = j - p .. j + p, a q outside [0, n_frames) reflected (q -> -q,
+ *          q -> 2 (n_frames - 1) - q: F.pad(mode = "reflect")) - a selection, so its bits are unique;
+ *   cost[u][i][j] = float(0.0 - S / double(n_heads)), S = ONE chain of fp64 additions from 0 of double(m[h][i][j]) in head
+ *          order.
+ * cost fp32 [n_utt, ld_t, ld_f]: every element is written - rows >= n_tok, frames >= n_frames and invalid utterances as
+ * WSAE_ALIGN_FILL (+inf).  n_bad int32 [n_utt]: 0 for a valid utterance, -1 where the sizes are invalid, else the number of
+ * non-finite values among those read.  status int64 [2], caller-owned and zero-initialised: status[0] += the invalid
+ * utterances, status[1] += the non-finite values (integer atomics).  z and m never exist in global memory.
+ *
+ * wsae_align_dtw.  cost fp32 [n_utt, ld_t, ld_f]; row_first, row_count, n_frames int32 [n_utt] in device memory: the
+ * alignment runs over rows row_first .. row_first + row_count - 1 (n = row_count rows) and frames 0 .. n_frames - 1
+ * (k frames) of cost[u] - the caller drops the start-of-transcript prefix and the end-of-text row this way.  n_bad is
+ * nullable (that of wsae_align_cost).  An utterance is invalid iff n_bad[u] != 0, row_first < 0, n < 1,
+ * n > WSAE_ALIGN_MAX_TOK, row_first + n > ld_t, k < 1, k > min(ld_f, WSAE_ALIGN_MAX_FRAMES), or a cost read is not
+ * finite.  The recurrence is Whisper's, D in fp32: D[-1][-1] = 0, every other border +inf,
+ *   D[i][j] = cost[i][j] + c (one fp32 addition), with c0 = D[i-1][j-1], c1 = D[i-1][j], c2 = D[i][j-1]:
+ *   c = c0 (diagonal) if c0 < c1 and c0 < c2; else c = c1 (up) if c1 < c0 and c1 < c2; else c = c2 (left).
+ * The path is walked back from (n - 1, k - 1) along the recorded choices; row 0 goes left, column 0 goes up.  Rows are
+ * numbered as in cost (row_first + i):
+ *   frame_pos int32 [n_utt, ld_f]: the largest row on the path at that frame (the row that starts there owns the frame,
+ *     as in Whisper's jumps); -1 from n_frames on and for invalid utterances;
+ *   tok_start int32 [n_utt, ld_t]: the first frame of every row on the path; tok_end: the start of the next row, n_frames
+ *     for the last one (a zero-length token has start == end); both -1 outside the rows and for invalid utterances;
+ *   path_cost fp32 [n_utt]: D[n-1][k-1] (WSAE_ALIGN_FILL where invalid); path_len int32 [n_utt]: the cells of the path (0
+ *     where invalid);
+ *   status int64 [2], zero-initialised: status[0] += the invalid utterances, status[1] += the non-finite costs read.
+ * Workspace (8-byte aligned): wsae_align_workspace_bytes(n_utt, ld_t, ld_f) - two bits per cell, the recorded choices; -1
+ * for invalid arguments; contents arbitrary on entry.  One workgroup per utterance; no wave waits for another anywhere but
+ * at a workgroup barrier, and every loop is bounded by the sizes.  n_utt == 0 returns WSAE_OK and touches nothing. */
+#define WSAE_DT_F16 2 /* wsae_align_cost only */
+#define WSAE_ALIGN_MAX_TOK 512
+#define WSAE_ALIGN_MAX_FRAMES 2048
+#define WSAE_ALIGN_MAX_HEADS 32
+#define WSAE_ALIGN_MAX_WIDTH 15
+#define WSAE_ALIGN_FILL (__builtin_inff())
+int wsae_align_cost(const void* w, int32_t w_dtype, int32_t n_utt, int32_t n_heads, int64_t ld_t, int64_t ld_f,
+                    const int32_t* n_tok, const int32_t* n_frames, int32_t width, float* cost, int32_t* n_bad, int64_t* status,
+                    void* stream);
+int64_t wsae_align_workspace_bytes(int32_t n_utt, int64_t max_tok, int64_t max_frames);
+int wsae_align_dtw(const float* cost, int32_t n_utt, int64_t ld_t, int64_t ld_f, const int32_t* row_first,
+                   const int32_t* row_count, const int32_t* n_frames, const int32_t* n_bad, int32_t* frame_pos,
+                   int32_t* tok_start, int32_t* tok_end, float* path_cost, int32_t* path_len, int64_t* status, void* workspace,
+                   int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

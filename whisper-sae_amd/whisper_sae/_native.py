@@ -36,6 +36,8 @@ DTW_MAX_LEN, DTW_MAX_K, DTW_COSINE, DTW_JACCARD = 64, 128, 0, 2  # wsae_dtw_matr
 ABX_ANY, ABX_WITHIN, ABX_ACROSS, ABX_MAX_CATS = 0, 1, 2, 1024  # wsae_abx_count
 PAIR_MAX_K, PAIR_MAX_TOKENS, PAIR_MAX_N, PAIR_BY_FEATURE, PAIR_BY_TOKEN = 128, 1 << 24, 32, 0, 1  # wsae_pair_update / wsae_pair_top
 PAIR_SCORES = ("count", "precision", "recall", "f1", "jaccard", "lift", "mean")  # WSAE_PAIR_COUNT .. WSAE_PAIR_MEAN, in order
+DT_F16 = 2  # wsae_align_cost only
+ALIGN_MAX_TOK, ALIGN_MAX_FRAMES, ALIGN_MAX_HEADS, ALIGN_MAX_WIDTH = 512, 2048, 32, 15  # wsae_align_cost / wsae_align_dtw
 BTK_STATE_WORDS = 8  # wsae_batch_topk_state: threshold, beta, last_t (f32), saturated_rows, kept, 3 reserved (i32)
 
 
@@ -177,6 +179,9 @@ SIGNATURES = {
     "wsae_pair_top_workspace_bytes": (_i64, [_i64, _i32]),
     "wsae_pair_top": (C.c_int, [_p, _p, _p, _i64, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, _i64,
                                 _p]),
+    "wsae_align_cost": (C.c_int, [_p, _i32, _i32, _i32, _i64, _i64, _p, _p, _i32, _p, _p, _p, _p]),
+    "wsae_align_workspace_bytes": (_i64, [_i32, _i64, _i64]),
+    "wsae_align_dtw": (C.c_int, [_p, _i32, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _p]),
     "wsae_relu_needs_hidden":(C.c_int, [_p, _i32]),
     "wsae_relu_forward": (C.c_int, [_p, _p, _p, _i32, _p, _i32, _f32, _p, _p, _p, _p, _p]),
     "wsae_relu_backward": (C.c_int, [_p, _p, _p, _i32, _p, _i32, _f32, _p, _p, _p, _p]),

@@ -12,9 +12,12 @@ of the curve's peaks against reference boundaries at every threshold), and code 
 their whole code, the units' purity, PNMI and adjusted Rand index against a label, and the unit strings), and ABX phone discrimination (DTW distances between segments of the code and the count of the
 triples in which a token lies closer to a token of its own phone than to one of another), and token association (exact
 counts of every (feature, token) pair that occurs, for vocabularies of 10^4 to 10^7 tokens, in a device hash table, with the
-top tokens of a feature and the top features of a token ranked on the device).  Mirrors the names of the reference's ``whisper_sae.analysis.feature_viz``
+top tokens of a feature and the top features of a token ranked on the device), and token alignment (a token label for
+every encoder frame from Whisper's cross-attention: the fused z-score / median / head-mean cost and dynamic time warping).  Mirrors the names of the reference's ``whisper_sae.analysis.feature_viz``
 that sit on that path."""
 
+from .alignment import (CrossAttentionTap, FrameAlignment, RawAlignment, align_tokens, align_weights, aligned_batches,
+                        alignment_heads)
 from .clustering import (ClusterScores, CodeKMeans, IterationStats, cluster_scores, collect_code_clusters,
                          unit_sequences)
 from .coactivation import (CoactivationNeighbors, CoactivationTracker, collect_coactivation,
@@ -53,4 +56,6 @@ __all__ = ["FeatureActivation", "TopKTracker", "collect_top_activations", "Neare
            "BoundaryCurve", "BoundaryScorer", "CodeDynamics", "DynamicsSummary", "LagStats", "boundaries_from_labels",
            "boundary_curve", "collect_code_dynamics", "detect_boundaries", "frame_similarity", "novelty", "ClusterScores", "CodeKMeans",
            "IterationStats", "cluster_scores", "collect_code_clusters", "unit_sequences", "AbxItems", "AbxScores", "collect_abx",
-           "items_from_labels", "segment_distances", "PairExport", "TokenAssociation", "TopPairs", "collect_token_association"]
+           "items_from_labels", "segment_distances", "PairExport", "TokenAssociation", "TopPairs", "collect_token_association",
+           "CrossAttentionTap", "FrameAlignment", "RawAlignment", "align_tokens", "align_weights", "aligned_batches",
+           "alignment_heads"]

@@ -11,7 +11,9 @@ same signatures and the same tensors.  The structure is this build's own:
   ``ActivationRing`` the trainer samples from in ONE kernel (``wsae_ring_push_layernorm``) and keeps nothing: extraction and
   SAE training share the GPU with no host round trip;
 * ``run_whisper_taps`` is the one place that drives the model (encoder pass, one decoder step from the start token): both
-  ``extract_features_batch`` here and ``extract_and_cache_features`` (data/feature_cache.py) go through it.
+  ``extract_features_batch`` here and ``extract_and_cache_features`` (data/feature_cache.py) go through it;
+  ``run_whisper_transcript`` is its teacher-forced counterpart (the decoder over a whole transcript), which the token
+  alignment of ``whisper_sae.analysis.alignment`` drives.
 
 The model is whatever ``transformers`` provides (``WhisperForConditionalGeneration``); this module only hooks it.
 """
@@ -175,6 +177,24 @@ def run_whisper_taps(model, extractor: WhisperActivationExtractor, input_feature
         start = torch.full((batch_size, 1), model.config.decoder_start_token_id, dtype=torch.long, device=device)
         model.model.decoder(input_ids=start, encoder_hidden_states=encoder_hidden)
     return batch_size
+
+
+def run_whisper_transcript(model, extractor: Optional[WhisperActivationExtractor], input_features: Tensor,
+                           decoder_input_ids: Tensor, device):
+    """The teacher-forced counterpart of ``run_whisper_taps``: the encoder once, then the decoder over the whole token
+    sequence ``decoder_input_ids [n_utt, n_tok]`` (the start-of-transcript prefix, the transcript, the end-of-text
+    token; padded at the end where the batch is ragged - the decoder is causal, so padding changes no earlier row).
+    ``extractor`` may be None; where it is given its hooks must be registered.  Returns ``(encoder_hidden, decoder_hidden)``,
+    the two final hidden states."""
+    del extractor  # (its hooks fire on their own; the argument keeps the two drivers' signatures alike)
+    input_features = input_features.to(device)
+    decoder_input_ids = decoder_input_ids.to(device=device, dtype=torch.long)
+    if decoder_input_ids.dim() != 2 or decoder_input_ids.size(0) != input_features.size(0):
+        raise ValueError(f"decoder_input_ids must be [n_utt, n_tok] for {input_features.size(0)} utterances, got "
+                         f"{tuple(decoder_input_ids.shape)}")
+    encoder_hidden = model.model.encoder(input_features).last_hidden_state
+    decoder_hidden = model.model.decoder(input_ids=decoder_input_ids, encoder_hidden_states=encoder_hidden).last_hidden_state
+    return encoder_hidden, decoder_hidden
 
 
 def extract_features_batch(model, input_features: Tensor, encoder_layers: list, decoder_layers: list,
