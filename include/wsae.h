@@ -1196,6 +1196,54 @@ int wsae_align_dtw(const float* cost, int32_t n_utt, int64_t ld_t, int64_t ld_f,
                    int32_t* tok_start, int32_t* tok_end, float* path_cost, int32_t* path_len, int64_t* status, void* workspace,
                    int64_t workspace_bytes, void* stream);
 
+/* ---- log-mel front end: framing, windowed DFT, mel filter bank, log and clamp ----------------------
+ * Waveforms in, Whisper's input_features out, as two kernels.  Ctx-free; the caller's stream, no allocation, no host
+ * synchronisation, no float atomics; argument errors are found on the host before any HIP call.  Every output of an
+ * utterance depends on that utterance alone, and every cell before the per-utterance clamp on its own frame alone: not on
+ * the tile, the batch position or the launch geometry.  tests/logmel_oracle.py restates all of this in numpy.
+ *
+ * Constants (Whisper's, compile-time): n_fft = WSAE_LOGMEL_NFFT = 400, hop = WSAE_LOGMEL_HOP = 160, WSAE_LOGMEL_BINS = 201
+ * frequency bins, n_mels 80 or 128.
+ *
+ * Batch.  x [n_utt] rows of stride ld_x (elements) of x_dtype WSAE_DT_F32 or WSAE_DT_I16 (int16 is scaled by 2^-15: exact);
+ * length int32 [n_utt] in DEVICE memory: utterance u has len = min(max(length[u], 0), max_length) valid samples and is
+ * zero from len to P = n_samples; nothing of x beyond len is read.  max_length (host) is the caller's bound on the lengths:
+ * 0 <= max_length <= min(ld_x, P).  P is a multiple of 160, 480 <= P <= 2^28; T = P / 160 frames.
+ *
+ * Frame t covers q = 160 t .. 160 t + 399 of the length-P signal padded by 200 reflected samples at both ends
+ * (np.pad(mode = "reflect") around P, not around length[u]): padded sample q is signal sample s = q - 200, with s < 0 -> -s
+ * and s >= P -> 2 (P - 1) - s.  Frame T + 1 of torch.stft does not exist here.
+ *
+ * DFT.  basis fp32 [400][WSAE_LOGMEL_COLS = 416], 16-byte aligned, supplied by the caller: column k (k = 0 .. 200) is the
+ * windowed cosine of bin k, column WSAE_LOGMEL_SIN_COL + k = 208 + k its sine; columns 201 .. 207 and 409 .. 415 are
+ * padding and must be zero.  (The Python layer builds w[n] cos(2 pi ((k n) mod 400) / 400) in fp64 with the periodic Hann
+ * window w and rounds once.)  The window lives in the table, the other operand is the raw sample:
+ *   re[t][k] = ONE chain acc = fmaf(sample[160 t + n], basis[n][k], acc) from acc = 0 over n = 0, 1, .. 399 in this order
+ * (v_mfma_f32_16x16x4_f32: bit for bit this chain); im[t][k] likewise with column 208 + k.
+ * Power.  p[t][k] = fl(fl(re re) + fl(im im)): two fp32 products, one fp32 sum, no fused multiply-add.
+ * Mel.  filt fp32 [201][n_mels] supplied by the caller;
+ *   mel[t][m] = ONE chain acc = fmaf(p[t][k], filt[k][m], acc) from 0 over k = 0 .. 200 in this order.
+ * Log.  v = log10f(mel) where mel > WSAE_LOGMEL_FLOOR = 1e-10f, else exactly -10 (log10(max(mel, 1e-10)); a NaN gives -10).
+ * Tail, per utterance and in fp32, the extractor's order: M[u] = max of v over all n_mels x T cells;
+ *   v = max(v, M[u] - 8); out = (v + 4) / 4.
+ * out fp32 [n_utt][n_mels][T] with strides ld_u, ld_m, 1 (ld_m >= T, ld_u >= n_mels ld_m, ld_m <= 2^21): the layout the
+ * encoder takes.  Only the cells (u, m, t < T) are written.  mel_power (nullable), same strides: mel[t][m] before floor and
+ * log.  With out, mel_power 16-byte aligned and ld_m, ld_u multiples of 4 the stores are 16 bytes wide, and write-through
+ * with 64-byte alignment and multiples of 16; any other alignment is served by 4-byte stores of the same values.
+ * Workspace (4-byte aligned): wsae_logmel_workspace_bytes(n_utt, n_samples, n_mels) - one maximum per 64 frames; -1 for
+ * invalid arguments; contents arbitrary on entry.  n_utt == 0 returns WSAE_OK and touches nothing. */
+#define WSAE_DT_I16 3 /* wsae_logmel only */
+#define WSAE_LOGMEL_NFFT 400
+#define WSAE_LOGMEL_HOP 160
+#define WSAE_LOGMEL_BINS 201
+#define WSAE_LOGMEL_COLS 416
+#define WSAE_LOGMEL_SIN_COL 208
+#define WSAE_LOGMEL_FLOOR 1e-10f
+int64_t wsae_logmel_workspace_bytes(int32_t n_utt, int64_t n_samples, int32_t n_mels);
+int wsae_logmel(const void* x, int32_t x_dtype, int32_t n_utt, int64_t ld_x, const int32_t* length, int64_t max_length,
+                int64_t n_samples, const float* basis, const float* filt, int32_t n_mels, float* out, int64_t ld_m, int64_t ld_u,
+                float* mel_power, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

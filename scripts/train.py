@@ -9,8 +9,9 @@ What differs:
 * the Whisper model comes from a LOCAL directory (``--whisper-path``, loaded with ``local_files_only``) or is a
   seeded random-init model of the configured geometry (``--whisper-random-init``: smoke runs and tests) - never a
   hub name: this build downloads nothing.  ``run()`` also takes a model OBJECT;
-* the mel features come from a tensor file (``--mel``: ``torch.save``d ``[N, n_mels, frames]``) or are synthetic
-  (``--synthetic-mel N``); audio decoding and the LibriSpeech loader stay outside this build;
+* the mel features come from a tensor file (``--mel``: ``torch.save``d ``[N, n_mels, frames]``), are synthetic
+  (``--synthetic-mel N``), or are computed on the device from waveforms (``--audio FILE``, ``--synthetic-audio N``);
+  decoding audio files and the LibriSpeech loader stay outside this build;
 * ``--stream-to-ring``: extraction pushes the layer-normed activations straight into the on-device ring the trainer
   samples from (one kernel per hooked call) - no ``.cpu()``, no cache file, no reload (SURVEY.md row N2);
 * cached activations are loaded once into the on-device ring buffer and batches are drawn there;
@@ -56,6 +57,11 @@ def parse_args(argv=None):
     ap.add_argument("--mel", type=str, default=None, help="torch.save'd mel features [N, n_mels, frames] to extract from")
     ap.add_argument("--synthetic-mel", type=int, default=0, metavar="N", help="extract from N synthetic mel clips")
     ap.add_argument("--mel-frames", type=int, default=3000, help="frames per synthetic clip (3000 = 30 s)")
+    ap.add_argument("--audio", type=str, default=None,
+                    help="torch.save'd waveforms at 16 kHz to extract from: a [N, samples] tensor (float32 or int16), or a dict "
+                         "with 'waveforms' and 'lengths'; the log-mel front end runs on the device")
+    ap.add_argument("--synthetic-audio", type=int, default=0, metavar="N",
+                    help="extract from N synthetic waveforms (seeded noise plus tones, lengths varied)")
     ap.add_argument("--stream-to-ring", action="store_true",
                     help="push extracted activations straight into the training ring (no cache files)")
     return ap.parse_args(argv)
@@ -104,9 +110,47 @@ def mel_batches(cfg: ExperimentConfig, args, model, batch_size: int = 16):
     elif args.synthetic_mel:
         g = torch.Generator().manual_seed(cfg.training.seed)
         mel = torch.randn(args.synthetic_mel, model.config.num_mel_bins, args.mel_frames, generator=g)
+    elif args.audio or args.synthetic_audio:
+        return audio_batches(cfg, args, model, batch_size)
     else:
         raise SystemExit("extraction needs mel features: --mel FILE or --synthetic-mel N (audio decoding is outside this build)")
     return [mel[i:i + batch_size] for i in range(0, mel.shape[0], batch_size)]
+
+
+def synthetic_audio(n: int, samples: int, seed: int):
+    """``(waveforms [n, samples] float32, lengths [n])``: seeded noise plus two tones per clip, zero beyond the length."""
+    g = torch.Generator().manual_seed(seed)
+    t = torch.arange(samples, dtype=torch.float32) / 16000.0
+    hz = 100.0 + 3000.0 * torch.rand(n, 2, generator=g)
+    wave = 0.05 * torch.randn(n, samples, generator=g)
+    wave += 0.3 * torch.sin(2 * torch.pi * hz[:, :1] * t) + 0.2 * torch.sin(2 * torch.pi * hz[:, 1:] * t)
+    lengths = torch.randint(samples // 2, samples + 1, (n,), generator=g)
+    lengths[0] = samples
+    wave[torch.arange(samples)[None, :] >= lengths[:, None]] = 0.0
+    return wave, lengths.to(torch.int32)
+
+
+def audio_batches(cfg: ExperimentConfig, args, model, batch_size: int = 16):
+    """``mel_batches`` from waveforms: ``LogMel`` turns every batch into ``[B, n_mels, --mel-frames]`` on the model's device."""
+    from whisper_sae.data import LogMel
+
+    samples = args.mel_frames * 160
+    if args.audio:
+        held = torch.load(args.audio, weights_only=True)
+        wave, lengths = (held["waveforms"], held.get("lengths")) if isinstance(held, dict) else (held, None)
+        if not isinstance(wave, torch.Tensor) or wave.ndim != 2:
+            raise SystemExit(f"--audio: expected [N, samples], got {tuple(getattr(wave, 'shape', ()))}")
+        if wave.shape[1] > samples:
+            raise SystemExit(f"--audio: {wave.shape[1]} samples per clip exceed --mel-frames {args.mel_frames} x 160")
+    else:
+        wave, lengths = synthetic_audio(args.synthetic_audio, samples, cfg.training.seed)
+    device = next(model.parameters()).device
+    frontend = LogMel(model.config.num_mel_bins, device=device, n_samples=samples)
+    out = []
+    for i in range(0, wave.shape[0], batch_size):
+        part = None if lengths is None else torch.as_tensor(lengths)[i:i + batch_size]
+        out.append(frontend(wave[i:i + batch_size].to(device), part))
+    return out
 
 
 def extract(cfg: ExperimentConfig, model, cache: FeatureCache, layers, device, batches, rings=None) -> dict:

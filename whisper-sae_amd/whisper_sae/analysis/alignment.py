@@ -254,16 +254,21 @@ def align_tokens(model, input_features: Tensor, decoder_input_ids: Tensor, *, n_
 
 def aligned_batches(model, batches: Iterable, *, encoder_layer: int, n_prefix: int,
                     heads: Optional[Sequence[Tuple[int, int]]] = None, width: int = 7, apply_layer_norm: bool = True,
-                    device="cuda"):
+                    device="cuda", frontend=None):
     """``(x [n_utt, T, D], frame_tokens [n_utt, T], frame_mask [n_utt, T])`` of every item ``(input_features,
     decoder_input_ids[, token_lengths[, num_frames]])``: the (layer-normed) output of encoder layer ``encoder_layer`` and the
     token label of every frame, from ONE forward - the activation extractor and the cross-attention tap together.  The
-    items are what ``collect_token_association`` and the other ``collect_*`` functions accept."""
+    items are what ``collect_token_association`` and the other ``collect_*`` functions accept.  With a ``frontend`` (a
+    ``whisper_sae.data.LogMel``) the first entry of an item may be a 2-D tensor of waveforms, or ``(waveforms, lengths)``:
+    it is converted to mel features on the device first."""
     _stream.need_gpu("aligned_batches", torch.device(device))
     for item in batches:
         if not isinstance(item, (tuple, list)) or not 2 <= len(item) <= 4:
             raise ValueError("an item must be (input_features, decoder_input_ids[, token_lengths[, num_frames]])")
         features, ids = item[0], item[1]
+        if frontend is not None:
+            from ..data.audio import features_from_batch
+            features = features_from_batch(frontend, features)
         lengths = item[2] if len(item) > 2 else None
         mel_frames = item[3] if len(item) > 3 else None
         extractor = WhisperActivationExtractor(model, encoder_layers=[encoder_layer], decoder_layers=[],

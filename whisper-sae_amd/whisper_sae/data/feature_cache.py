@@ -274,13 +274,15 @@ class FeatureCache:
 
 def extract_and_cache_features(whisper_model, processor, audio_dataloader, cache: Optional[FeatureCache], encoder_layers: list,
                                decoder_layers: list, device="cpu", max_samples: Optional[int] = None,
-                               rings: Optional[dict] = None, show_progress: bool = True) -> dict:
+                               rings: Optional[dict] = None, show_progress: bool = True, frontend=None) -> dict:
     """Run ``whisper_model`` over ``audio_dataloader`` and keep the tapped layers' activations (reference
     feature_cache.py:200-306; same positional arguments - ``processor`` is accepted and, as in the reference, unused).
 
     Every batch (a tensor of mel features ``[B, n_mels, frames]``, or a tuple / list whose first item is one) goes
     through the encoder and, when decoder layers are tapped, one decoder step from the start token; the final LayerNorm
-    is applied to each tapped output (``apply_layer_norm=True`` as the reference hard-codes).  Batches are taken while
+    is applied to each tapped output (``apply_layer_norm=True`` as the reference hard-codes).  With a ``frontend`` (a
+    ``LogMel``; not in the reference) a batch that is a 2-D tensor of waveforms, or a tuple / list ``(waveforms, lengths,
+    ...)``, is converted to mel features on the device first; 3-D batches pass through as without it.  Batches are taken while
     ``num_samples < max_samples`` - whole batches, so the count can overshoot exactly as the reference's does.
 
     Where the activations go:
@@ -293,6 +295,7 @@ def extract_and_cache_features(whisper_model, processor, audio_dataloader, cache
     Returns ``{"num_samples": n, "tokens": {(component, layer): rows}}``.
     """
     from ..sae.hooks import WhisperActivationExtractor, flatten_activations, run_whisper_taps
+    from .audio import features_from_batch
 
     del processor  # (the reference's signature; its body never reads it either)
     rings = dict(rings or {})
@@ -326,7 +329,9 @@ def extract_and_cache_features(whisper_model, processor, audio_dataloader, cache
             for batch in audio_dataloader:
                 if num_samples >= limit:
                     break
-                if isinstance(batch, (list, tuple)):
+                if frontend is not None:
+                    batch = features_from_batch(frontend, batch)
+                elif isinstance(batch, (list, tuple)):
                     batch = batch[0]
                 batch_size = run_whisper_taps(whisper_model, extractor, batch, device)
                 for component, layer in to_disk:
