@@ -53,18 +53,6 @@ struct AssignArgs {
     unsigned long long* totals;
 };
 
-__device__ __forceinline__ int cl_wave_min_i(int v) {
-    const int lane = threadIdx.x & 63;
-    int o;
-    o = (int)lane_xor_u32<32>((uint32_t)v, lane); v = o < v ? o : v;
-    o = (int)lane_xor_u32<16>((uint32_t)v, lane); v = o < v ? o : v;
-    o = (int)lane_xor_u32<8>((uint32_t)v, lane); v = o < v ? o : v;
-    o = (int)lane_xor_u32<4>((uint32_t)v, lane); v = o < v ? o : v;
-    o = (int)lane_xor_u32<2>((uint32_t)v, lane); v = o < v ? o : v;
-    o = (int)lane_xor_u32<1>((uint32_t)v, lane); v = o < v ? o : v;
-    return v;
-}
-
 // the entries of `mask` (bits of the lanes whose col is a column), CL_FB at a time, in ascending position
 template <int CT>
 __device__ __forceinline__ void cl_add_entries(unsigned long long mask, float v, int col, const AssignArgs& a, int lane,
@@ -119,7 +107,7 @@ __device__ __forceinline__ void cl_arg_max(const float (&score)[CT], int C, int 
         const int c = t * 64 + lane;
         if (c < C && c != skip && score[t] == mx) am = c;
     }
-    am = __builtin_amdgcn_readfirstlane(cl_wave_min_i(am));
+    am = __builtin_amdgcn_readfirstlane(wave_min_i(am));
     arg = -1;
     top = -INFINITY;
     if (am == INT_MAX) return;  // (no cluster but skip; wave-uniform)

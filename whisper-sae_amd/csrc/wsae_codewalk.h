@@ -3,10 +3,12 @@
 // wave-per-row front end (probe_row_columns, probe_load_row).  Host side: the predicates behind the *_workspace_bytes
 // queries (code_args_ok for a code with a feature window, column_code_ok for one with a column map) and the CW_REQUIRE_*
 // checks of the entry points: k, rows, window, hidden, the column code, a single lag, the entry lists of a transposed plan,
-// the size of the workspace and its alignment.  Included by wsae_groupstats.hip (pooling), wsae_runs.hip, wsae_sta.hip,
-// wsae_profile.hip and wsae_labels.hip (the entry-per-thread walk), wsae_probe.hip and wsae_regress.hip (the wave-per-row
-// front end, the column code) and, for the checks alone, wsae_coact.hip.  (align256 and min64 live in wsae_common.h:
-// wsae_match.hip needs them and walks no code.)
+// the size of the workspace and its alignment.  Included by wsae_groupstats.hip (pooling), wsae_runs.hip, wsae_labels.hip
+// (the entry-per-thread walk), wsae_regress.hip, wsae_cluster.hip (the wave-per-row front end, the column code),
+// wsae_dyn_canon.h (the same front end, for wsae_dynamics.hip and wsae_abx.hip), for the checks alone wsae_coact.hip,
+// wsae_pairs.hip and wsae_align.hip, and through wsae_lists.h - the plumbing of the analyses that build per-key lists -
+// by wsae_sta.hip, wsae_probe.hip, wsae_profile.hip and wsae_feature_topk.hip.  (align256, min64 and the wave helpers
+// live in wsae_common.h: wsae_match.hip needs them and walks no code.)
 #pragma once
 #include <limits.h>
 

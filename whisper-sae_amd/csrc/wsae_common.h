@@ -215,6 +215,28 @@ __device__ __forceinline__ int wave_sum_i(int v) {
     v += (int)lane_xor_u32<1>((uint32_t)v, lane);
     return v;
 }
+__device__ __forceinline__ int wave_min_i(int v) {
+    const int lane = threadIdx.x & 63;
+    int o;
+    o = (int)lane_xor_u32<32>((uint32_t)v, lane); v = o < v ? o : v;
+    o = (int)lane_xor_u32<16>((uint32_t)v, lane); v = o < v ? o : v;
+    o = (int)lane_xor_u32<8>((uint32_t)v, lane); v = o < v ? o : v;
+    o = (int)lane_xor_u32<4>((uint32_t)v, lane); v = o < v ? o : v;
+    o = (int)lane_xor_u32<2>((uint32_t)v, lane); v = o < v ? o : v;
+    o = (int)lane_xor_u32<1>((uint32_t)v, lane); v = o < v ? o : v;
+    return v;
+}
+
+// the value another lane holds (v_readlane: `lane` is wave-uniform)
+__device__ __forceinline__ float lane_f32(float x, int lane) {
+    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), lane));
+}
+__device__ __forceinline__ double lane_f64(double x, int lane) {
+    const long long b = __double_as_longlong(x);
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)b, lane);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(b >> 32), lane);
+    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
 
 // deterministic block reduction of one float per thread (blockDim.x multiple of 64, <= 1024);
 // result valid in thread 0.  `scratch` must hold blockDim.x/64 floats.

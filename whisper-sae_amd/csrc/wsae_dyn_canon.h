@@ -32,10 +32,6 @@ struct DynArgs {
     unsigned long long* total_rows;
 };
 
-__device__ __forceinline__ float lane_f32(float x, int lane) {
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), lane));
-}
-
 __global__ __launch_bounds__(DY_BLOCK) void dyn_canon_kernel(DynArgs a) {
     const int lane = threadIdx.x & 63;
     const int64_t wave = (int64_t)blockIdx.x * (DY_BLOCK / 64) + (threadIdx.x >> 6);

@@ -8,13 +8,15 @@
 // the earlier of two equal values at the boundary (its `act_value > heap[0][0]` is strict) and the list is
 // deterministic because (value, ordinal) is unique inside one feature.
 //
-// Four launches per update, all HBM-bound integer/byte work (12 B per entry read twice + 8 B written once):
+// Four launches per update, all HBM-bound integer/byte work (12 B per entry read twice + 8 B written once); the head of
+// the workspace (list_head) and the scan are shared with the sampler of wsae_profile.hip (wsae_lists.h):
 //   count    histogram of the positive entries per feature (+ the total)
-//   scan     exclusive scan of the histogram (one block)
+//   scan     exclusive scan of the histogram (one block, count_scan_kernel): int32 offsets and cursors, which is why a
+//            call takes at most 2^31 - 1 entries
 //   scatter  entries grouped by feature (order inside a group is arbitrary; the merge is order-independent)
 //   merge    one wave per feature: the list lives one element per lane, candidates that beat the current minimum
 //            are inserted by a lane shift
-#include "wsae_common.h"
+#include "wsae_lists.h"
 
 namespace {
 
@@ -43,38 +45,6 @@ __global__ __launch_bounds__(FT_BLOCK) void ft_count_kernel(const float* __restr
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o, 64);
     if ((threadIdx.x & 63) == 0 && mine) atomicAdd(total, mine);
-}
-
-// offs[f] = sum of cnt[<f]; cursor[f] = offs[f]
-__global__ __launch_bounds__(1024) void ft_scan_kernel(const int32_t* __restrict__ cnt, int32_t* __restrict__ offs,
-                                                       int32_t* __restrict__ cursor, int H) {
-    __shared__ int32_t wsum[16];
-    __shared__ int32_t carry;
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    if (t == 0) carry = 0;
-    __syncthreads();
-    for (int base = 0; base < H; base += 1024) {
-        const int f = base + t;
-        const int32_t c = f < H ? cnt[f] : 0;
-        int32_t s = c;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int32_t u = __shfl_up(s, o, 64);
-            if (lane >= o) s += u;
-        }
-        if (lane == 63) wsum[w] = s;
-        __syncthreads();
-        int32_t before = carry;
-        for (int i = 0; i < w; ++i) before += wsum[i];
-        if (f < H) {
-            offs[f] = before + s - c;
-            cursor[f] = before + s - c;
-        }
-        __syncthreads();
-        if (t == 1023) carry = before + s;
-        __syncthreads();
-    }
-    if (t == 0) offs[H] = carry;
 }
 
 template <bool DENSE>
@@ -159,10 +129,9 @@ __global__ __launch_bounds__(FT_BLOCK) void ft_merge_kernel(const int32_t* __res
 }  // namespace
 
 extern "C" int64_t wsae_feature_topk_workspace_bytes(int64_t max_entries, int32_t H) {
-    if (max_entries < 0 || H < 1) return -1;
-    // cnt[H] | offs[H+1] | cursor[H] (int32, rounded up to 256 B) | ent_val[max_entries] | ent_row[max_entries]
-    const int64_t head = ((3 * (int64_t)H + 1) * 4 + 255) / 256 * 256;
-    return head + 8 * max_entries;
+    if (max_entries < 0 || max_entries > INT_MAX || H < 1) return -1;
+    // the head of H lists | ent_val[max_entries] | ent_row[max_entries]
+    return list_head(nullptr, H).bytes + 8 * max_entries;
 }
 
 extern "C" int wsae_feature_topk_update(const float* vals, const int32_t* idx, int64_t rows, int32_t width, int32_t H,
@@ -176,34 +145,33 @@ extern "C" int wsae_feature_topk_update(const float* vals, const int32_t* idx, i
                  (long long)rows, width, keep);
     WSAE_REQUIRE(idx || width == H, "wsae_feature_topk_update: a dense matrix (idx == null) must be [rows][H]");
     WSAE_REQUIRE(rows < (1ll << 32), "wsae_feature_topk_update: at most 2^32 - 1 rows per call");
+    WSAE_REQUIRE(rows * width <= INT_MAX, "wsae_feature_topk_update: at most 2^31 - 1 entries per call (got %lld rows of %d)",
+                 (long long)rows, width);
     const int64_t n = rows * width;
     WSAE_REQUIRE(workspace_bytes >= wsae_feature_topk_workspace_bytes(n, H),
                  "wsae_feature_topk_update: workspace too small (%lld < %lld)", (long long)workspace_bytes,
                  (long long)wsae_feature_topk_workspace_bytes(n, H));
     if (n == 0) return WSAE_OK;
-    int32_t* cnt = (int32_t*)workspace;
-    int32_t* offs = cnt + H;
-    int32_t* cursor = offs + H + 1;
-    const int64_t head = ((3 * (int64_t)H + 1) * 4 + 255) / 256 * 256;
-    float* ent_val = (float*)((char*)workspace + head);
+    const ListHead h = list_head(workspace, H);
+    float* ent_val = (float*)((char*)workspace + h.bytes);
     uint32_t* ent_row = (uint32_t*)(ent_val + n);
     const int grid = (int)(ceil_div64(n, FT_BLOCK) < 8192 ? ceil_div64(n, FT_BLOCK) : 8192);
-    WSAE_HIP_CHECK(hipMemsetAsync(cnt, 0, sizeof(int32_t) * H, stream));
+    WSAE_HIP_CHECK(hipMemsetAsync(h.cnt, 0, sizeof(int32_t) * H, stream));
     if (idx) {
-        ft_count_kernel<false><<<grid, FT_BLOCK, 0, stream>>>(vals, idx, n, width, H, cnt, (unsigned long long*)total_active);
+        ft_count_kernel<false><<<grid, FT_BLOCK, 0, stream>>>(vals, idx, n, width, H, h.cnt, (unsigned long long*)total_active);
     } else {
-        ft_count_kernel<true><<<grid, FT_BLOCK, 0, stream>>>(vals, idx, n, width, H, cnt, (unsigned long long*)total_active);
+        ft_count_kernel<true><<<grid, FT_BLOCK, 0, stream>>>(vals, idx, n, width, H, h.cnt, (unsigned long long*)total_active);
     }
     WSAE_LAUNCH_CHECK();
-    ft_scan_kernel<<<1, 1024, 0, stream>>>(cnt, offs, cursor, H);
+    count_scan_kernel<1024><<<1, 1024, 0, stream>>>(h.cnt, h.offs, h.cursor, H);
     WSAE_LAUNCH_CHECK();
     if (idx) {
-        ft_scatter_kernel<false><<<grid, FT_BLOCK, 0, stream>>>(vals, idx, n, width, H, cursor, ent_val, ent_row);
+        ft_scatter_kernel<false><<<grid, FT_BLOCK, 0, stream>>>(vals, idx, n, width, H, h.cursor, ent_val, ent_row);
     } else {
-        ft_scatter_kernel<true><<<grid, FT_BLOCK, 0, stream>>>(vals, idx, n, width, H, cursor, ent_val, ent_row);
+        ft_scatter_kernel<true><<<grid, FT_BLOCK, 0, stream>>>(vals, idx, n, width, H, h.cursor, ent_val, ent_row);
     }
     WSAE_LAUNCH_CHECK();
-    ft_merge_kernel<<<ceil_div(H, FT_BLOCK / 64), FT_BLOCK, 0, stream>>>(offs, ent_val, ent_row, H, keep, ord_base, top_vals,
+    ft_merge_kernel<<<ceil_div(H, FT_BLOCK / 64), FT_BLOCK, 0, stream>>>(h.offs, ent_val, ent_row, H, keep, ord_base, top_vals,
                                                                          top_ord, top_cnt);
     WSAE_LAUNCH_CHECK();
     return WSAE_OK;

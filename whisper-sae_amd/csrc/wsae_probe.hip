@@ -2,12 +2,13 @@
 // dense [frames, H] matrix and without float atomics.  An iteration of the fit is two sparse products over the code.
 //
 // wsae_probe_plan transposes the code once (it depends on the code, seg and col_of only).  A stable counting sort in
-// four launches, the scheme of wsae_sta_update written for this entry list (every first-active entry that has a column,
-// no lags, no onset rule):
+// four launches, the scheme of wsae_sta_update - with its chunking of the rows, its scan and the body of its offsets
+// kernel, all in wsae_lists.h - and a walk of its own for this entry list (every first-active entry that has a column, no
+// lags, no onset rule):
 //   1. probe_walk_kernel<false>: a single-wave workgroup owns (chunk of consecutive rows, tile of PB_TILE columns), walks
 //      its rows in order, one lane per entry, and counts the entries of each column in LDS: one row of [chunks, P].
-//   2. probe_scan_kernel: per column the exclusive prefix over the chunks and its total; probe_offsets_kernel (one
-//      workgroup): the exclusive prefix of the totals - col_ptr - and nnz.
+//   2. chunk_scan_kernel: per column the exclusive prefix over the chunks and its total; probe_offsets_kernel<false> (one
+//      workgroup, list_offsets with the policy ProbeOffsets): the exclusive prefix of the totals - col_ptr - and nnz.
 //   3. probe_walk_kernel<true>: the same walk, taking slots from LDS cursors that start at the scanned positions, so a
 //      column's list is in ascending row.  Slots from cap on are not written.
 // The entries of one row name distinct columns (first-active entries name distinct features, col_of maps them to
@@ -25,7 +26,7 @@
 // probe_partial_kernel gives a job and 64 classes to a wave (lanes as classes, eight error rows in flight, the job's
 // column found by bisection of the job numbers) and stores the partial, probe_sum_kernel adds a column's partials in
 // order.  gb the same way over chunks of WSAE_PROBE_CHUNK consecutive rows.
-#include "wsae_codewalk.h"
+#include "wsae_lists.h"
 
 // every fp32 multiply and add below rounds on its own, as the numpy mirror of the tests does
 #pragma clang fp contract(off)
@@ -33,8 +34,6 @@
 namespace {
 
 constexpr int PB_TILE = 4096;        // columns per walk job: 16 KB of counts, or 32 KB of cursors
-constexpr int PB_MAX_CHUNKS = 1024;  // rows of the count table
-constexpr int PB_MIN_CHUNK = 64;     // rows per chunk at least
 constexpr int PB_ROWS = 4;           // rows of the code whose loads are issued before the first of them is processed
 constexpr int PB_MAX_BLOCKS = 1 << 20;
 constexpr int PB_FWD_BLOCK = 256;        // four waves, a row each
@@ -113,75 +112,40 @@ __global__ __launch_bounds__(64) void probe_walk_kernel(const float* __restrict_
     }
 }
 
-// table[ch][p] := the entries of p in the chunks before ch; lens[p] := all of them
-__global__ __launch_bounds__(256) void probe_scan_kernel(int32_t* __restrict__ table, int n_chunks, int P,
-                                                         int32_t* __restrict__ lens) {
-    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (p >= P) return;
-    int run = 0;
-#pragma unroll 8
-    for (int ch = 0; ch < n_chunks; ++ch) {
-        const int c = table[(int64_t)ch * P + p];
-        table[(int64_t)ch * P + p] = run;
-        run += c;
-    }
-    lens[p] = run;
-}
-
-// One workgroup: out[p] = the sum of len(p') over p' < p, out[P] = the total (also to *total when given).  CHUNKED: len is
-// the number of WSAE_PROBE_CHUNK pieces of column p's list clipped to cap (in: col_ptr); otherwise in is the lengths.
+// list_offsets for the plan: out [n + 1], out[n] = the total (also to *total when given).  CHUNKED: a length is the number
+// of WSAE_PROBE_CHUNK pieces of column p's list clipped to cap (in: col_ptr); otherwise in is the lengths.
 template <bool CHUNKED>
-__global__ __launch_bounds__(1024) void probe_offsets_kernel(const void* __restrict__ in, int P, int64_t cap,
-                                                             int64_t* __restrict__ out, int64_t* __restrict__ total) {
-    __shared__ long long part[1024];
-    const int tid = threadIdx.x;
-    const int per = (P + 1023) / 1024;
-    const int64_t lo64 = (int64_t)tid * per;
-    const int lo = lo64 < P ? (int)lo64 : P;
-    const int hi = lo64 + per < P ? (int)(lo64 + per) : P;
-    auto len = [&](int p) -> long long {
+struct ProbeOffsets {
+    static constexpr bool CLASSES = false, TOTAL = true;
+    const void* in;
+    int n;
+    int64_t cap;
+    int64_t* out;
+    int64_t* total;
+    __device__ long long len(int p) const {
         if (!CHUNKED) return ((const int32_t*)in)[p];
         const int64_t* cp = (const int64_t*)in;
         const int64_t a = cp[p] < cap ? cp[p] : cap, b = cp[p + 1] < cap ? cp[p + 1] : cap;
         return b > a ? (b - a + PB_CHUNK - 1) / PB_CHUNK : 0;
-    };
-    long long sum = 0;
-    for (int p = lo; p < hi; ++p) sum += len(p);
-    part[tid] = sum;
-    __syncthreads();
-    if (tid == 0) {
-        long long run = 0;
-        for (int i = 0; i < 1024; ++i) {
-            const long long s = part[i];
-            part[i] = run;
-            run += s;
-        }
-        out[P] = run;
-        if (total) total[0] = run;
     }
-    __syncthreads();
-    long long run = part[tid];
-    for (int p = lo; p < hi; ++p) {
-        const long long n = len(p);  // (read before out[p] is written: in and out never alias)
-        out[p] = run;
-        run += n;
-    }
+};
+
+template <bool CHUNKED>
+__global__ __launch_bounds__(1024) void probe_offsets_kernel(const void* __restrict__ in, int P, int64_t cap,
+                                                             int64_t* __restrict__ out, int64_t* __restrict__ total) {
+    list_offsets(ProbeOffsets<CHUNKED>{in, P, cap, out, total});
 }
 
 struct PlanWs {
-    int64_t chunk_rows;
-    int n_chunks;
+    ChunkPlan c;
     int64_t off_table, off_lens, bytes;
 };
 
 PlanWs plan_ws(int64_t n_rows, int P) {
     PlanWs w;
-    w.chunk_rows = ceil_div64(n_rows, PB_MAX_CHUNKS);
-    if (w.chunk_rows < PB_MIN_CHUNK) w.chunk_rows = PB_MIN_CHUNK;
-    w.n_chunks = (int)ceil_div64(n_rows, w.chunk_rows);
-    if (w.n_chunks < 1) w.n_chunks = 1;
+    w.c = chunk_plan(n_rows);
     w.off_table = 0;
-    w.off_lens = w.off_table + align256(4 * (int64_t)w.n_chunks * P);
+    w.off_lens = w.off_table + align256(4 * (int64_t)w.c.n_chunks * P);
     w.bytes = w.off_lens + align256(4 * (int64_t)P);
     return w;
 }
@@ -209,18 +173,6 @@ struct FwdArgs {
     unsigned long long* loss_q;
     unsigned long long* confusion;
 };
-
-__device__ __forceinline__ int wave_min_i(int v) {
-    const int lane = threadIdx.x & 63;
-    int o;
-    o = (int)lane_xor_u32<32>((uint32_t)v, lane); v = o < v ? o : v;
-    o = (int)lane_xor_u32<16>((uint32_t)v, lane); v = o < v ? o : v;
-    o = (int)lane_xor_u32<8>((uint32_t)v, lane); v = o < v ? o : v;
-    o = (int)lane_xor_u32<4>((uint32_t)v, lane); v = o < v ? o : v;
-    o = (int)lane_xor_u32<2>((uint32_t)v, lane); v = o < v ? o : v;
-    o = (int)lane_xor_u32<1>((uint32_t)v, lane); v = o < v ? o : v;
-    return v;
-}
 
 // the entries of `mask` (bits of the lanes whose col is a column), PB_FB at a time, in ascending position
 template <int CT>
@@ -482,13 +434,13 @@ extern "C" int wsae_probe_plan(const float* vals, const int32_t* idx, int32_t k,
     int32_t* table = (int32_t*)((char*)workspace + w.off_table);
     int32_t* lens = (int32_t*)((char*)workspace + w.off_lens);
     const int n_tiles = ceil_div(n_cols, PB_TILE);
-    const int64_t jobs = (int64_t)w.n_chunks * n_tiles;
+    const int64_t jobs = (int64_t)w.c.n_chunks * n_tiles;
     const int grid = (int)(jobs < PB_MAX_BLOCKS ? jobs : PB_MAX_BLOCKS);
-    probe_walk_kernel<false><<<grid, 64, 0, st>>>(vals, idx, k, hidden, seg, n_rows, w.chunk_rows, w.n_chunks, col_of, n_cols,
+    probe_walk_kernel<false><<<grid, 64, 0, st>>>(vals, idx, k, hidden, seg, n_rows, w.c.chunk_rows, w.c.n_chunks, col_of, n_cols,
                                                   n_tiles, table, col_ptr, t_row, t_val, cap);
-    probe_scan_kernel<<<ceil_div(n_cols, 256), 256, 0, st>>>(table, w.n_chunks, n_cols, lens);
+    chunk_scan_kernel<256><<<ceil_div(n_cols, 256), 256, 0, st>>>(table, w.c.n_chunks, n_cols, lens);
     probe_offsets_kernel<false><<<1, 1024, 0, st>>>(lens, n_cols, 0, col_ptr, nnz);
-    probe_walk_kernel<true><<<grid, 64, 0, st>>>(vals, idx, k, hidden, seg, n_rows, w.chunk_rows, w.n_chunks, col_of, n_cols,
+    probe_walk_kernel<true><<<grid, 64, 0, st>>>(vals, idx, k, hidden, seg, n_rows, w.c.chunk_rows, w.c.n_chunks, col_of, n_cols,
                                                  n_tiles, table, col_ptr, t_row, t_val, cap);
     WSAE_LAUNCH_CHECK();
     return WSAE_OK;

@@ -13,7 +13,8 @@
 // wsae_sample_update: per (feature, value stratum) the m activations with the smallest keys ever offered, the key
 // being a hash of (ordinal, feature, seed) above the ordinal: a bottom-m sketch, i.e. a uniform sample without
 // replacement that does not depend on call order or batching and merges exactly.  The four launches of
-// wsae_feature_topk.hip - count, scan, scatter by list, one wave per list merging - with a pre-filter in the first pass:
+// wsae_feature_topk.hip - count, scan (count_scan_kernel and the workspace head of wsae_lists.h, shared with that file),
+// scatter by list, one wave per list merging - with a pre-filter in the first pass:
 // an entry whose key is not below the last key of its list as the list stands when the call begins can never enter
 // (lists only tighten), so its `seen` is counted and it goes no further.
 //
@@ -23,7 +24,7 @@
 // global loads.
 #include <limits.h>
 
-#include "wsae_codewalk.h"
+#include "wsae_lists.h"
 
 namespace {
 
@@ -151,38 +152,6 @@ __global__ __launch_bounds__(PF_BLOCK) void sample_pass_kernel(CodeArgs a, Sampl
     }
 }
 
-// offs[i] = sum of cnt[< i], offs[n] the total; cursor[i] = offs[i]
-__global__ __launch_bounds__(1024) void sample_scan_kernel(const int32_t* __restrict__ cnt, int32_t* __restrict__ offs,
-                                                           int32_t* __restrict__ cursor, int n) {
-    __shared__ int32_t wsum[16];
-    __shared__ int32_t carry;
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    if (t == 0) carry = 0;
-    __syncthreads();
-    for (int base = 0; base < n; base += 1024) {
-        const int i = base + t;
-        const int32_t c = i < n ? cnt[i] : 0;
-        int32_t s = c;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int32_t u = __shfl_up(s, o, 64);
-            if (lane >= o) s += u;
-        }
-        if (lane == 63) wsum[w] = s;
-        __syncthreads();
-        int32_t before = carry;
-        for (int q = 0; q < w; ++q) before += wsum[q];
-        if (i < n) {
-            offs[i] = before + s - c;
-            cursor[i] = before + s - c;
-        }
-        __syncthreads();
-        if (t == 1023) carry = before + s;
-        __syncthreads();
-    }
-    if (t == 0) offs[n] = carry;
-}
-
 // one wave per list; lane l holds list element l (m <= 64), ascending by key; lanes from m on hold SM_EMPTY
 __global__ __launch_bounds__(PF_BLOCK) void sample_merge_kernel(const int32_t* __restrict__ offs,
                                                                 const unsigned long long* __restrict__ ent_key,
@@ -236,8 +205,6 @@ __global__ __launch_bounds__(PF_BLOCK) void sample_merge_kernel(const int32_t* _
     }
 }
 
-inline int64_t sample_head_bytes(int64_t n_lists) { return ((3 * n_lists + 1) * 4 + 255) / 256 * 256; }
-
 inline bool sample_args_ok(int64_t n_rows, int k, int hidden, int64_t f_lo, int64_t f_cols, int S, int m) {
     return code_args_ok(n_rows, k, WSAE_PROFILE_MAX_K, hidden, f_lo, f_cols) && n_rows * k <= INT_MAX && S >= 1 &&
            S <= WSAE_SAMPLE_MAX_STRATA && m >= 1 && m <= WSAE_SAMPLE_MAX_KEEP && f_cols * S < INT_MAX;
@@ -283,8 +250,8 @@ extern "C" int wsae_profile_update(const float* vals, const int32_t* idx, int32_
 extern "C" int64_t wsae_sample_workspace_bytes(int64_t n_rows, int32_t k, int32_t hidden, int32_t f_lo, int32_t f_cols,
                                                int32_t n_strata, int32_t keep) {
     if (!sample_args_ok(n_rows, k, hidden, f_lo, f_cols, n_strata, keep)) return -1;
-    // cnt | offs (+ 1) | cursor per list (int32, rounded up to 256 B) | ent_key [n_rows k] uint64 | ent_val [n_rows k] fp32
-    return sample_head_bytes((int64_t)f_cols * n_strata) + 12 * n_rows * k;
+    // the head of f_cols n_strata lists | ent_key [n_rows k] uint64 | ent_val [n_rows k] fp32
+    return list_head(nullptr, (int64_t)f_cols * n_strata).bytes + 12 * n_rows * k;
 }
 
 extern "C" int wsae_sample_update(const float* vals, const int32_t* idx, int32_t k, int32_t hidden, const int32_t* seg,
@@ -307,25 +274,22 @@ extern "C" int wsae_sample_update(const float* vals, const int32_t* idx, int32_t
     WSAE_REQUIRE(ord_base >= 0 && ord_base + n_rows <= (1ll << 31),
                  "wsae_sample_update: the ordinals %lld + [0, %lld) leave [0, 2^31)", (long long)ord_base, (long long)n_rows);
     const int64_t n = n_rows * k, n_lists = (int64_t)f_cols * n_strata;
-    const int64_t head = sample_head_bytes(n_lists), need = head + 12 * n;
-    CW_REQUIRE_WORKSPACE("wsae_sample_update", workspace, workspace_bytes, need, n_rows);
+    const ListHead h = list_head(workspace, n_lists);
+    CW_REQUIRE_WORKSPACE("wsae_sample_update", workspace, workspace_bytes, h.bytes + 12 * n, n_rows);
     if (n_rows == 0) return WSAE_OK;
     hipStream_t st = (hipStream_t)stream;
-    int32_t* cnt = (int32_t*)workspace;
-    int32_t* offs = cnt + n_lists;
-    int32_t* cursor = offs + n_lists + 1;
-    unsigned long long* ent_key = (unsigned long long*)((char*)workspace + head);
+    unsigned long long* ent_key = (unsigned long long*)((char*)workspace + h.bytes);
     float* ent_val = (float*)(ent_key + n);
     CodeArgs a = {vals, idx, seg, n, k, f_lo, f_cols};
     SampleArgs sa = {edges, n_strata, keep, seed, ord_base, (const unsigned long long*)keys, seen};
-    WSAE_HIP_CHECK(hipMemsetAsync(cnt, 0, sizeof(int32_t) * n_lists, st));
-    sample_pass_kernel<false><<<pf_grid(n), PF_BLOCK, 0, st>>>(a, sa, cnt, ent_key, ent_val);
+    WSAE_HIP_CHECK(hipMemsetAsync(h.cnt, 0, sizeof(int32_t) * n_lists, st));
+    sample_pass_kernel<false><<<pf_grid(n), PF_BLOCK, 0, st>>>(a, sa, h.cnt, ent_key, ent_val);
     WSAE_LAUNCH_CHECK();
-    sample_scan_kernel<<<1, 1024, 0, st>>>(cnt, offs, cursor, (int)n_lists);
+    count_scan_kernel<1024><<<1, 1024, 0, st>>>(h.cnt, h.offs, h.cursor, (int)n_lists);
     WSAE_LAUNCH_CHECK();
-    sample_pass_kernel<true><<<pf_grid(n), PF_BLOCK, 0, st>>>(a, sa, cursor, ent_key, ent_val);
+    sample_pass_kernel<true><<<pf_grid(n), PF_BLOCK, 0, st>>>(a, sa, h.cursor, ent_key, ent_val);
     WSAE_LAUNCH_CHECK();
-    sample_merge_kernel<<<(int)ceil_div64(n_lists, PF_BLOCK / 64), PF_BLOCK, 0, st>>>(offs, ent_key, ent_val, (int)n_lists, keep,
+    sample_merge_kernel<<<(int)ceil_div64(n_lists, PF_BLOCK / 64), PF_BLOCK, 0, st>>>(h.offs, ent_key, ent_val, (int)n_lists, keep,
                                                                                      (unsigned long long*)keys, svals);
     WSAE_LAUNCH_CHECK();
     return WSAE_OK;

@@ -8,10 +8,10 @@
 //      in order, one lane per entry, and counts the triggers of each tile feature in LDS; the counts become one row of the
 //      [chunks, f_cols] table.  The per-feature "last seen on row" cell gives both "an index repeated within a row counts
 //      once" and the onset rule (a chunk first looks at the row in front of it, without counting).
-//   2. sta_scan_kernel: per feature the exclusive prefix over the chunks (feature-major, chunk-minor) and its total.
-//      sta_offsets_kernel (one workgroup): the exclusive prefix of the totals, and the features ordered by the length of
-//      their lists, long ones first (33 classes by the position of the leading bit; the order inside a class is free and
-//      changes no result).
+//   2. chunk_scan_kernel (wsae_lists.h): per feature the exclusive prefix over the chunks (feature-major, chunk-minor)
+//      and its total.  sta_offsets_kernel (one workgroup, list_offsets of wsae_lists.h with the policy StaOffsets): the
+//      exclusive prefix of the totals, and the features ordered by the length of their lists, long ones first (33 classes
+//      by the position of the leading bit; the order inside a class is free and changes no result).
 //   3. sta_walk_kernel<true>: the same walk, now taking slots from LDS cursors that start at the scanned positions: the
 //      list of a feature holds (row, weight) in ascending row.  A stable counting sort; the trigger rules are applied here.
 //   4. sta_accum_kernel: a single-wave workgroup owns (feature, tile of 64 channels); lane = channel, the L accumulators
@@ -20,15 +20,15 @@
 //      the last L rows sit in a 128-slot LDS ring (row, weight, segment); lane j looks at the slot of lag j, a ballot gives
 //      the lags that have a term, and the weight of lag j reaches the other lanes by v_readlane.  wsum and cnt of lag j
 //      are kept by lane j of the feature's first channel tile.
+// The chunking of the rows, the scan and the body of the offsets kernel are shared with wsae_probe.hip (wsae_lists.h); the
+// walk and its trigger rules are this file's.
 #include <limits.h>
 
-#include "wsae_codewalk.h"
+#include "wsae_lists.h"
 
 namespace {
 
 constexpr int ST_TILE = 4096;        // features per walk job: 16 KB of rows + 4 KB of tags + 16 / 32 KB of counts / cursors
-constexpr int ST_MAX_CHUNKS = 1024;  // rows of the count table
-constexpr int ST_MIN_CHUNK = 64;     // rows per chunk at least
 constexpr int ST_MAX_BLOCKS = 1 << 20;
 constexpr int ST_ROWS = 4;           // rows of the code whose loads are issued before the first of them is processed
 constexpr int ST_RB = 8;             // signal rows per block of the accumulation
@@ -150,70 +150,24 @@ __global__ __launch_bounds__(64) void sta_walk_kernel(const float* __restrict__ 
     }
 }
 
-// table[ch][f] := the triggers of f in the chunks before ch; lens[f] := all of them
-__global__ __launch_bounds__(256) void sta_scan_kernel(int32_t* __restrict__ table, int n_chunks, int f_cols,
-                                                       int32_t* __restrict__ lens) {
-    const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (f >= f_cols) return;
-    int run = 0;
-#pragma unroll 8
-    for (int ch = 0; ch < n_chunks; ++ch) {
-        const int c = table[(int64_t)ch * f_cols + f];
-        table[(int64_t)ch * f_cols + f] = run;
-        run += c;
-    }
-    lens[f] = run;
-}
-
 __device__ __forceinline__ int sta_class(int len) { return len > 0 ? 32 - __clz(len) : 0; }  // 0 (empty) .. 31
 
-// one workgroup: base[f] = the lists before f; order = the features by class of length, long ones first
+// list_offsets for the trigger lists: out = base [n] (no element n: the total goes nowhere); order = the features by class
+// of length, long ones first
+struct StaOffsets {
+    static constexpr bool CLASSES = true, TOTAL = false;
+    const int32_t* lens;
+    int n;
+    int64_t* out;
+    int32_t* order;
+    __device__ long long len(int f) const { return lens[f]; }
+    __device__ void count(int* cls, int f) const { atomicAdd(&cls[sta_class(lens[f])], 1); }
+    __device__ void place(int* cls, int f) const { order[atomicAdd(&cls[sta_class(lens[f])], 1)] = f; }
+};
+
 __global__ __launch_bounds__(1024) void sta_offsets_kernel(const int32_t* __restrict__ lens, int f_cols, int64_t* __restrict__ base,
                                                            int32_t* __restrict__ order) {
-    __shared__ long long part[1024];
-    __shared__ int cls[33];
-    const int tid = threadIdx.x;
-    const int per = (f_cols + 1023) / 1024;
-    const int64_t lo64 = (int64_t)tid * per;
-    const int lo = lo64 < f_cols ? (int)lo64 : f_cols;
-    const int hi = lo64 + per < f_cols ? (int)(lo64 + per) : f_cols;
-    if (tid < 33) cls[tid] = 0;
-    __syncthreads();
-    long long sum = 0;
-    for (int f = lo; f < hi; ++f) {
-        sum += lens[f];
-        atomicAdd(&cls[sta_class(lens[f])], 1);
-    }
-    part[tid] = sum;
-    __syncthreads();
-    if (tid == 0) {
-        long long run = 0;
-        for (int i = 0; i < 1024; ++i) {
-            const long long s = part[i];
-            part[i] = run;
-            run += s;
-        }
-        int at = 0;
-        for (int b = 32; b >= 0; --b) {
-            const int n = cls[b];
-            cls[b] = at;
-            at += n;
-        }
-    }
-    __syncthreads();
-    long long run = part[tid];
-    for (int f = lo; f < hi; ++f) {
-        base[f] = run;
-        run += lens[f];
-        order[atomicAdd(&cls[sta_class(lens[f])], 1)] = f;
-    }
-}
-
-__device__ __forceinline__ double sta_readlane_f64(double x, int lane) {
-    const long long b = __double_as_longlong(x);
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)b, lane);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(b >> 32), lane);
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+    list_offsets(StaOffsets{lens, f_cols, base, order});
 }
 
 // LP: lags the lane's registers hold (L <= LP); DT: the signal's type
@@ -309,7 +263,7 @@ __global__ __launch_bounds__(64) void sta_accum_kernel(const int32_t* __restrict
                     if (((m >> g) & 15ull) == 0ull) continue;
 #pragma unroll
                     for (int j = g; j < g + 4 && j < LP; ++j)
-                        if ((m >> j) & 1ull) a[j] = fma(sta_readlane_f64(wd, j), yd, a[j]);  // (the product is exact in fp64)
+                        if ((m >> j) & 1ull) a[j] = fma(lane_f64(wd, j), yd, a[j]);  // (the product is exact in fp64)
                 }
             }
             next += used;
@@ -326,22 +280,18 @@ __global__ __launch_bounds__(64) void sta_accum_kernel(const int32_t* __restrict
 }
 
 struct StaPlan {
-    int64_t chunk_rows;
-    int n_chunks;
+    ChunkPlan c;
     int64_t off_row, off_w, off_table, off_lens, off_base, off_order, bytes;
 };
 
 StaPlan sta_plan(int64_t n_rows, int k, int f_cols) {
     StaPlan p;
-    p.chunk_rows = ceil_div64(n_rows, ST_MAX_CHUNKS);
-    if (p.chunk_rows < ST_MIN_CHUNK) p.chunk_rows = ST_MIN_CHUNK;
-    p.n_chunks = (int)ceil_div64(n_rows, p.chunk_rows);
-    if (p.n_chunks < 1) p.n_chunks = 1;
+    p.c = chunk_plan(n_rows);
     const int64_t entries = n_rows * k;
     p.off_row = 0;
     p.off_w = p.off_row + align256(4 * entries);
     p.off_table = p.off_w + align256(4 * entries);
-    p.off_lens = p.off_table + align256(4 * (int64_t)p.n_chunks * f_cols);
+    p.off_lens = p.off_table + align256(4 * (int64_t)p.c.n_chunks * f_cols);
     p.off_base = p.off_lens + align256(4 * (int64_t)f_cols);
     p.off_order = p.off_base + align256(8 * (int64_t)f_cols);
     p.bytes = p.off_order + align256(4 * (int64_t)f_cols);
@@ -388,15 +338,15 @@ extern "C" int wsae_sta_update(const float* vals, const int32_t* idx, int32_t k,
     int64_t* base = (int64_t*)(ws + p.off_base);
     int32_t* order = (int32_t*)(ws + p.off_order);
     const int n_tiles = ceil_div(f_cols, ST_TILE);
-    const int64_t walk_jobs = (int64_t)p.n_chunks * n_tiles;
+    const int64_t walk_jobs = (int64_t)p.c.n_chunks * n_tiles;
     const int walk_grid = (int)(walk_jobs < ST_MAX_BLOCKS ? walk_jobs : ST_MAX_BLOCKS);
     const int onset = trigger == WSAE_STA_TRIGGER_ONSET, one = weight == WSAE_STA_WEIGHT_ONE;
     const size_t lds_count = ST_TILE * 9, lds_scatter = ST_TILE * 13;
 #define ST_WALK(SC_, NP_, LDS_)                                                                                           \
-    sta_walk_kernel<SC_, NP_><<<walk_grid, 64, LDS_, st>>>(vals, idx, k, seg, n_rows, p.chunk_rows, p.n_chunks, f_lo, f_cols, \
+    sta_walk_kernel<SC_, NP_><<<walk_grid, 64, LDS_, st>>>(vals, idx, k, seg, n_rows, p.c.chunk_rows, p.c.n_chunks, f_lo, f_cols, \
                                                            n_tiles, onset, one, table, base, ent_row, ent_w)
     if (k <= 64) ST_WALK(false, 1, lds_count); else ST_WALK(false, 2, lds_count);
-    sta_scan_kernel<<<ceil_div(f_cols, 256), 256, 0, st>>>(table, p.n_chunks, f_cols, lens);
+    chunk_scan_kernel<256><<<ceil_div(f_cols, 256), 256, 0, st>>>(table, p.c.n_chunks, f_cols, lens);
     sta_offsets_kernel<<<1, 1024, 0, st>>>(lens, f_cols, base, order);
     if (k <= 64) ST_WALK(true, 1, lds_scatter); else ST_WALK(true, 2, lds_scatter);
 #undef ST_WALK
