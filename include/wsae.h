@@ -1232,7 +1232,7 @@ int wsae_align_dtw(const float* cost, int32_t n_utt, int64_t ld_t, int64_t ld_f,
  * with 64-byte alignment and multiples of 16; any other alignment is served by 4-byte stores of the same values.
  * Workspace (4-byte aligned): wsae_logmel_workspace_bytes(n_utt, n_samples, n_mels) - one maximum per 64 frames; -1 for
  * invalid arguments; contents arbitrary on entry.  n_utt == 0 returns WSAE_OK and touches nothing. */
-#define WSAE_DT_I16 3 /* wsae_logmel only */
+#define WSAE_DT_I16 3 /* wsae_logmel and wsae_clip_extract only */
 #define WSAE_LOGMEL_NFFT 400
 #define WSAE_LOGMEL_HOP 160
 #define WSAE_LOGMEL_BINS 201
@@ -1243,6 +1243,46 @@ int64_t wsae_logmel_workspace_bytes(int32_t n_utt, int64_t n_samples, int32_t n_
 int wsae_logmel(const void* x, int32_t x_dtype, int32_t n_utt, int64_t ld_x, const int32_t* length, int64_t max_length,
                 int64_t n_samples, const float* basis, const float* filt, int32_t n_mels, float* out, int64_t ld_m, int64_t ld_u,
                 float* mel_power, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---- audio clip export: cut, peak, gain, fades and PCM conversion of many clips at once -------------
+ * n_clips sample ranges of a device-resident bank of waveforms go to one output buffer, each at its own offset, as two
+ * kernels.  Ctx-free; the caller's stream, no allocation, no host synchronisation, no float atomics; argument errors are
+ * found on the host before any HIP call.  A clip's output depends on that clip's samples and table entries alone: not on
+ * the other clips, their order, the tile or the alignment of either side.  tests/clip_oracle.py restates all of this in numpy.
+ *
+ * Bank.  x [n_utt] rows of stride ld_x (elements) of x_dtype WSAE_DT_F32 or WSAE_DT_I16 (int16 is scaled by 2^-15: exact);
+ * length int32 [n_utt] in DEVICE memory: utterance u has L_u = min(max(length[u], 0), max_length) samples and nothing of x
+ * at or beyond L_u is read.  max_length (host) is the caller's bound on the lengths, 0 <= max_length <= ld_x, below 2^31.
+ * Samples must be finite.
+ * Clip tables, all in DEVICE memory (a selection made on the device feeds the call without a host round trip):
+ * clip_utt int32, clip_start int64, clip_count int32, clip_off int64, each [n_clips].  max_count (host, 0 .. 2^30) bounds the
+ * counts - it sizes the grid and the workspace - and a larger count is clamped to it; a negative count is 0.
+ * Bounds of clip c: u = clip_utt[c]; s0 = max(clip_start[c], 0); e = min(s0 + count, L_u); n = max(e - s0, 0).  A negative
+ * start moves to 0 and keeps its count; the end is cut at the length (the reference's extract_clip).
+ * Peak.  m = max_j |x_j| over the n samples, float32 (0 for an empty clip).
+ * Arithmetic, float32, no fused multiply-add, IEEE division:
+ *   gain_mode WSAE_CLIP_GAIN_PEAK and m > 0: y_j = fl(fl(x_j / m) * target);  otherwise y_j = x_j.
+ *   fade = F >= 1: y_j = fl(y_j * r_j), r_j = fl(float(min(min(j, n - 1 - j) + 1, F)) / float(F));  F = 0: no fade.
+ * Output at out[clip_off[c] + j], j < n.  out_dtype WSAE_DT_F32: y_j.  WSAE_DT_I16: clamp(rintf(fl(y_j * 32767)), -32768,
+ * 32767) - round half to even.  The one exception: GAIN_NONE, F = 0, int16 in and int16 out copies the samples unchanged.
+ * out_len int32 [n_clips]: n, or -1 for an invalid clip - u outside [0, n_utt), clip_off[c] < 0 or clip_off[c] + n >
+ * out_elems - of which no sample is written.  out_peak float32 [n_clips], nullable: m (0 for an invalid clip).
+ * Only the n cells of a clip are written, gaps between clips stay untouched, so one call serves the padded
+ * [n_clips][ld] layout and a montage with silences between the clips.  Output ranges must not overlap (the caller's
+ * contract).  x and out are aligned to their element size; any clip_start and clip_off are served: the bulk of a clip leaves
+ * as 16-byte stores from the first 64-byte boundary of its output on, write-through, the ends elementwise, same values.
+ * Workspace (4-byte aligned): wsae_clip_workspace_bytes(n_clips, max_count) - one float per clip and WSAE_CLIP_TILE
+ * samples of max_count, at least one per clip; -1 for invalid arguments; contents arbitrary on entry.  n_clips == 0 returns
+ * WSAE_OK and touches nothing. */
+#define WSAE_CLIP_TILE 4096 /* samples per workgroup */
+#define WSAE_CLIP_GAIN_NONE 0
+#define WSAE_CLIP_GAIN_PEAK 1
+int64_t wsae_clip_workspace_bytes(int32_t n_clips, int64_t max_count);
+int wsae_clip_extract(const void* x, int32_t x_dtype, int32_t n_utt, int64_t ld_x, const int32_t* length, int64_t max_length,
+                      int32_t n_clips, const int32_t* clip_utt, const int64_t* clip_start, const int32_t* clip_count,
+                      int64_t max_count, const int64_t* clip_off, int32_t gain_mode, float target, int32_t fade, void* out,
+                      int32_t out_dtype, int64_t out_elems, int32_t* out_len, float* out_peak, void* workspace,
+                      int64_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,275 @@
+// Audio clip export: cut n_clips ragged sample ranges out of a device-resident bank of waveforms, find
+// each clip's peak, apply the gain and the linear fades, convert to float32 or 16-bit PCM and store every clip at its own
+// offset of one output buffer - two kernels on the caller's stream.  The contract, operation by operation, is in
+// include/wsae.h; tests/clip_oracle.py restates it.
+//
+// Both kernels run one workgroup of 256 threads per (clip, tile of WSAE_CLIP_TILE = 4096 samples), flattened into gridDim.x;
+// a tile at or beyond the clip's n samples exits after the clip's bounds are resolved (a handful of scalar loads), which is
+// what balances ragged event clips.
+// clip_peak_kernel reduces |x| over its tile (DPP wave maximum, then LDS) into one workspace float per (clip, tile).
+// clip_write_kernel reduces the clip's tile maxima (a float maximum: any order gives the same bits), reads its tile again
+//   (from L2 / Infinity Cache: the peak kernel has just read it), computes the output values and stages them in LDS, then
+//   stores them.  The staging is what decouples the two alignments: a clip starts at an arbitrary sample, so the source is
+//   read as scalars up to the first 16-byte boundary, 16 bytes per lane from there, scalars behind the last whole vector
+//   (for_tile); the output begins at an arbitrary clip_off, so the image sits in LDS shifted by the elements that lead up to
+//   the output's first 64-byte boundary, and from that boundary on a lane stores 16 aligned bytes, a wave instruction whole
+//   64-byte pieces: those go write-through, the at most three vectors behind the last whole piece plain,
+//   the ragged ends elementwise.  The same values whatever the alignment.  The LDS writes of the staging are scalar (the
+//   shift is arbitrary) and conflict 4- or 8-way; at 16 KB per tile that is a few hundred cycles against the thousands the
+//   tile's bytes take at the memory rate.
+// When neither the gain nor out_peak needs the peak (WSAE_CLIP_GAIN_NONE, out_peak null) the peak kernel is not launched.
+#include <math.h>
+
+#include "wsae_common.h"
+
+// (x / m) * target * r is a division and two products, each rounded
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int CL_BLOCK = 256, CL_WAVES = CL_BLOCK / 64;
+constexpr int CL_TILE = WSAE_CLIP_TILE;
+constexpr int64_t CL_MAX_COUNT = 1ll << 30;  // tile offsets and n stay inside an int
+static_assert(CL_TILE % (8 * CL_BLOCK) == 0, "a tile is a whole number of 16-byte vectors per thread, int16 and float32");
+
+struct ClipArgs {
+    const void* x;
+    int64_t ld_x;
+    const int32_t* length;
+    int32_t n_utt, max_length;
+    const int32_t* clip_utt;
+    const int64_t* clip_start;
+    const int32_t* clip_count;
+    const int64_t* clip_off;
+    int32_t max_count, tiles;  // tiles: per clip in the grid and in the workspace (at least one)
+    int32_t gain_mode, fade, need_peak;
+    float target, scale;       // scale: float -> int16 (32767; 32768 for the plain int16 copy, which is then exact)
+    void* out;
+    int64_t out_elems;
+    int32_t* out_len;
+    float* out_peak;
+    float* tile_max;
+};
+
+struct ClipSpan {
+    int64_t src, off;  // first sample in x (elements), first cell in out
+    int n;             // samples
+    bool valid;
+};
+
+// every value here is workgroup-uniform: c comes from blockIdx
+__device__ __forceinline__ ClipSpan clip_span(const ClipArgs& a, int c) {
+    ClipSpan s;
+    const int u = a.clip_utt[c];
+    const int64_t s0 = a.clip_start[c] > 0 ? a.clip_start[c] : 0;
+    const int cnt = min(max(a.clip_count[c], 0), a.max_count);
+    const bool in = u >= 0 && u < a.n_utt;
+    const int len = in ? min(max(a.length[u], 0), a.max_length) : 0;
+    s.n = s0 < len ? (int)min64(cnt, len - s0) : 0;
+    s.off = a.clip_off[c];
+    s.valid = in && s.off >= 0 && s.off <= a.out_elems - s.n;
+    s.src = (int64_t)u * a.ld_x + s0;
+    return s;
+}
+
+// f(j, x_j) for every j in [0, m) exactly once, x_j = element first + j of x as float: scalar loads up to the first 16-byte
+// boundary, one 16-byte load per lane from there (all of a thread's loads issue before the first use), scalar loads behind
+// the last whole vector.  Nothing outside [first, first + m) is read.  m <= CL_TILE.
+template <int DT, class F>
+__device__ __forceinline__ void for_tile(const void* x, int64_t first, int m, F&& f) {
+    typedef short short8 __attribute__((ext_vector_type(8)));
+    constexpr int VE = DT == WSAE_DT_I16 ? 8 : 4, ES = 16 / VE, PER = CL_TILE / VE / CL_BLOCK;
+    const char* p = (const char*)x + first * ES;
+    const int lead = min((int)(((16 - ((uintptr_t)p & 15)) & 15) / ES), m);
+    const int nvec = (m - lead) / VE, done = lead + nvec * VE;
+    auto one = [&](int j) -> float {
+        if constexpr (DT == WSAE_DT_I16) return (float)((const int16_t*)p)[j] * 0x1p-15f;
+        else return ((const float*)p)[j];
+    };
+    const int tid = threadIdx.x;
+    if constexpr (DT == WSAE_DT_I16) {
+        const short8* pv = (const short8*)(p + lead * ES);
+        short8 q[PER];
+#pragma unroll
+        for (int k = 0; k < PER; ++k)
+            if (tid + k * CL_BLOCK < nvec) q[k] = pv[tid + k * CL_BLOCK];
+        if (tid < lead) f(tid, one(tid));
+#pragma unroll
+        for (int k = 0; k < PER; ++k) {
+            const int v = tid + k * CL_BLOCK;
+            if (v < nvec) {
+#pragma unroll
+                for (int i = 0; i < VE; ++i) f(lead + v * VE + i, (float)q[k][i] * 0x1p-15f);
+            }
+        }
+    } else {
+        const f32x4* pv = (const f32x4*)(p + lead * ES);
+        f32x4 q[PER];
+#pragma unroll
+        for (int k = 0; k < PER; ++k)
+            if (tid + k * CL_BLOCK < nvec) q[k] = pv[tid + k * CL_BLOCK];
+        if (tid < lead) f(tid, one(tid));
+#pragma unroll
+        for (int k = 0; k < PER; ++k) {
+            const int v = tid + k * CL_BLOCK;
+            if (v < nvec) {
+#pragma unroll
+                for (int i = 0; i < VE; ++i) f(lead + v * VE + i, q[k][i]);
+            }
+        }
+    }
+    if (done + tid < m) f(done + tid, one(done + tid));  // (fewer than VE of them)
+}
+
+// the maximum of one value per thread, in every thread
+__device__ __forceinline__ float block_max(float v, float* s_red) {
+    v = wave_max(v);
+    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3]));
+}
+
+template <int DT>
+__global__ __launch_bounds__(CL_BLOCK) void clip_peak_kernel(ClipArgs a) {
+    __shared__ float s_red[CL_WAVES];
+    const int c = blockIdx.x / a.tiles, t = blockIdx.x % a.tiles, j0 = t * CL_TILE;
+    const ClipSpan s = clip_span(a, c);
+    if (!s.valid || j0 >= s.n) return;
+    float mx = 0.f;
+    for_tile<DT>(a.x, s.src + j0, min(CL_TILE, s.n - j0), [&](int, float x) { mx = fmaxf(mx, fabsf(x)); });
+    mx = block_max(mx, s_red);
+    if (threadIdx.x == 0) a.tile_max[(int64_t)c * a.tiles + t] = mx;
+}
+
+template <int OT> struct ClipOut { typedef float type; };
+template <> struct ClipOut<WSAE_DT_I16> { typedef int16_t type; };
+
+template <int OT>
+__device__ __forceinline__ typename ClipOut<OT>::type clip_convert(float y, float scale) {
+    if constexpr (OT == WSAE_DT_I16) return (int16_t)(int)fminf(fmaxf(rintf(y * scale), -32768.0f), 32767.0f);
+    else return y;
+}
+
+template <int DT, int OT>
+__global__ __launch_bounds__(CL_BLOCK) void clip_write_kernel(ClipArgs a) {
+    typedef typename ClipOut<OT>::type T;
+    constexpr int VE = 16 / (int)sizeof(T), PIECE = 64 / (int)sizeof(T), PER = CL_TILE / VE / CL_BLOCK;
+    __shared__ __attribute__((aligned(64))) T s_y[CL_TILE + PIECE];
+    __shared__ float s_red[CL_WAVES];
+    const int c = blockIdx.x / a.tiles, t = blockIdx.x % a.tiles, j0 = t * CL_TILE, tid = threadIdx.x;
+    const ClipSpan s = clip_span(a, c);
+    const int tiles = s.valid ? (s.n + CL_TILE - 1) / CL_TILE : 0;
+    if (t != 0 && t >= tiles) return;
+    float m = 0.f;
+    if (a.need_peak) {
+        for (int i = tid; i < tiles; i += CL_BLOCK) m = fmaxf(m, a.tile_max[(int64_t)c * a.tiles + i]);
+        m = block_max(m, s_red);
+    }
+    if (t == 0 && tid == 0) {  // the clip's first workgroup reports, also where the clip is empty or invalid
+        a.out_len[c] = s.valid ? s.n : -1;
+        if (a.out_peak) a.out_peak[c] = m;
+    }
+    if (t >= tiles) return;
+
+    const int mlen = min(CL_TILE, s.n - j0);
+    T* po = (T*)a.out + s.off + j0;
+    // lead: the cells in front of the output's first 64-byte boundary; cell j of the tile sits at s_y[j + shift], so that
+    // the cell on that boundary is at s_y[0] or s_y[PIECE]
+    const int lead = min((int)(((64 - ((uintptr_t)po & 63)) & 63) / sizeof(T)), mlen);
+    const int shift = (PIECE - lead) % PIECE;
+    const bool gain = a.gain_mode == WSAE_CLIP_GAIN_PEAK && m > 0.f;
+    const float target = a.target, scale = a.scale, flen = (float)a.fade;
+    const int fade = a.fade, last = s.n - 1;
+    for_tile<DT>(a.x, s.src + j0, mlen, [&](int jl, float x) {
+        float y = gain ? (x / m) * target : x;
+        if (fade > 0) {
+            const int j = j0 + jl;
+            y = y * ((float)min(min(j, last - j) + 1, fade) / flen);
+        }
+        s_y[jl + shift] = clip_convert<OT>(y, scale);
+    });
+    __syncthreads();
+
+    if (tid < lead) po[tid] = s_y[tid + shift];
+    const int nvec = (mlen - lead) / VE, whole = nvec & ~3;  // whole: the vectors that make up whole 64-byte pieces
+    const float4* sv = (const float4*)(s_y + lead + shift);
+    T* pb = po + lead;
+    const __amdgpu_buffer_rsrc_t rs = wt_rsrc(pb);  // (based at the tile: the 32-bit offsets below stay under 16 KB)
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+        const int v = tid + k * CL_BLOCK;
+        if (v < whole) wt_store4(rs, (int64_t)v * 16, sv[v]);
+        else if (v < nvec) *(float4*)(pb + v * VE) = sv[v];
+    }
+    const int done = lead + nvec * VE;
+    if (done + tid < mlen) po[done + tid] = s_y[done + tid + shift];
+}
+
+inline bool dtype_ok(int dt) { return dt == WSAE_DT_F32 || dt == WSAE_DT_I16; }
+inline int64_t clip_tiles(int64_t max_count) { return max_count > CL_TILE ? ceil_div64(max_count, CL_TILE) : 1; }
+
+template <int DT>
+void launch_write(int out_dtype, unsigned grid, hipStream_t st, const ClipArgs& a) {
+    if (out_dtype == WSAE_DT_I16) clip_write_kernel<DT, WSAE_DT_I16><<<grid, CL_BLOCK, 0, st>>>(a);
+    else clip_write_kernel<DT, WSAE_DT_F32><<<grid, CL_BLOCK, 0, st>>>(a);
+}
+
+}  // namespace
+
+extern "C" int64_t wsae_clip_workspace_bytes(int32_t n_clips, int64_t max_count) {
+    if (n_clips < 0 || max_count < 0 || max_count > CL_MAX_COUNT) return -1;
+    return align256((int64_t)sizeof(float) * n_clips * clip_tiles(max_count));
+}
+
+extern "C" int wsae_clip_extract(const void* x, int32_t x_dtype, int32_t n_utt, int64_t ld_x, const int32_t* length,
+                                 int64_t max_length, int32_t n_clips, const int32_t* clip_utt, const int64_t* clip_start,
+                                 const int32_t* clip_count, int64_t max_count, const int64_t* clip_off, int32_t gain_mode,
+                                 float target, int32_t fade, void* out, int32_t out_dtype, int64_t out_elems, int32_t* out_len,
+                                 float* out_peak, void* workspace, int64_t workspace_bytes, void* stream) {
+    WSAE_REQUIRE(x && length && clip_utt && clip_start && clip_count && clip_off && out && out_len, "wsae_clip_extract: null pointer");
+    WSAE_REQUIRE(dtype_ok(x_dtype), "wsae_clip_extract: unknown x_dtype %d (float32 or int16)", x_dtype);
+    WSAE_REQUIRE(dtype_ok(out_dtype), "wsae_clip_extract: unknown out_dtype %d (float32 or int16)", out_dtype);
+    WSAE_REQUIRE(n_utt >= 0, "wsae_clip_extract: n_utt must not be negative (got %d)", n_utt);
+    WSAE_REQUIRE(n_clips >= 0, "wsae_clip_extract: n_clips must not be negative (got %d)", n_clips);
+    WSAE_REQUIRE(max_count >= 0 && max_count <= CL_MAX_COUNT, "wsae_clip_extract: need 0 <= max_count <= %lld (got %lld)",
+                 (long long)CL_MAX_COUNT, (long long)max_count);
+    WSAE_REQUIRE(max_length >= 0 && max_length <= 0x7fffffffll, "wsae_clip_extract: need 0 <= max_length < 2^31 (got %lld)",
+                 (long long)max_length);
+    WSAE_REQUIRE(ld_x >= max_length, "wsae_clip_extract: ld_x %lld is below max_length %lld", (long long)ld_x, (long long)max_length);
+    WSAE_REQUIRE(out_elems >= 0, "wsae_clip_extract: out_elems must not be negative (got %lld)", (long long)out_elems);
+    WSAE_REQUIRE(gain_mode == WSAE_CLIP_GAIN_NONE || gain_mode == WSAE_CLIP_GAIN_PEAK, "wsae_clip_extract: unknown gain_mode %d",
+                 gain_mode);
+    WSAE_REQUIRE(isfinite(target), "wsae_clip_extract: target must be finite");
+    WSAE_REQUIRE(fade >= 0, "wsae_clip_extract: fade must not be negative (got %d)", fade);
+    const uintptr_t xa = x_dtype == WSAE_DT_I16 ? 1 : 3, oa = out_dtype == WSAE_DT_I16 ? 1 : 3;
+    WSAE_REQUIRE(((uintptr_t)x & xa) == 0 && ((uintptr_t)out & oa) == 0, "wsae_clip_extract: x and out must be aligned to their elements");
+    WSAE_REQUIRE((((uintptr_t)length | (uintptr_t)clip_utt | (uintptr_t)clip_count | (uintptr_t)out_len | (uintptr_t)out_peak) & 3) == 0 &&
+                     (((uintptr_t)clip_start | (uintptr_t)clip_off) & 7) == 0,
+                 "wsae_clip_extract: the int32 / float tables must be 4-byte aligned, clip_start and clip_off 8-byte");
+    const int64_t need = wsae_clip_workspace_bytes(n_clips, max_count);
+    WSAE_REQUIRE(workspace_bytes >= need && (workspace || n_clips == 0), "wsae_clip_extract: workspace too small (%lld < %lld)",
+                 (long long)(workspace ? workspace_bytes : 0), (long long)need);
+    WSAE_REQUIRE(((uintptr_t)workspace & 3) == 0, "wsae_clip_extract: the workspace must be 4-byte aligned");
+    const int64_t tiles = clip_tiles(max_count);
+    WSAE_REQUIRE((int64_t)n_clips * tiles <= 0x7fffffffll, "wsae_clip_extract: n_clips * tiles of max_count is too large for one launch");
+    if (n_clips == 0) return WSAE_OK;
+    hipStream_t st = (hipStream_t)stream;
+    ClipArgs a;
+    a.x = x; a.ld_x = ld_x; a.length = length; a.n_utt = n_utt; a.max_length = (int32_t)max_length;
+    a.clip_utt = clip_utt; a.clip_start = clip_start; a.clip_count = clip_count; a.clip_off = clip_off;
+    a.max_count = (int32_t)max_count; a.tiles = (int32_t)tiles;
+    a.gain_mode = gain_mode; a.fade = fade; a.need_peak = gain_mode == WSAE_CLIP_GAIN_PEAK || out_peak != nullptr;
+    a.target = target;
+    a.scale = gain_mode == WSAE_CLIP_GAIN_NONE && fade == 0 && x_dtype == WSAE_DT_I16 ? 32768.0f : 32767.0f;
+    a.out = out; a.out_elems = out_elems; a.out_len = out_len; a.out_peak = out_peak; a.tile_max = (float*)workspace;
+    const unsigned grid = (unsigned)(n_clips * tiles);
+    if (a.need_peak) {
+        if (x_dtype == WSAE_DT_I16) clip_peak_kernel<WSAE_DT_I16><<<grid, CL_BLOCK, 0, st>>>(a);
+        else clip_peak_kernel<WSAE_DT_F32><<<grid, CL_BLOCK, 0, st>>>(a);
+        WSAE_LAUNCH_CHECK();
+    }
+    if (x_dtype == WSAE_DT_I16) launch_write<WSAE_DT_I16>(out_dtype, grid, st, a);
+    else launch_write<WSAE_DT_F32>(out_dtype, grid, st, a);
+    WSAE_LAUNCH_CHECK();
+    return WSAE_OK;
+}

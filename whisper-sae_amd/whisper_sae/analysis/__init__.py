@@ -13,11 +13,15 @@ their whole code, the units' purity, PNMI and adjusted Rand index against a labe
 triples in which a token lies closer to a token of its own phone than to one of another), and token association (exact
 counts of every (feature, token) pair that occurs, for vocabularies of 10^4 to 10^7 tokens, in a device hash table, with the
 top tokens of a feature and the top features of a token ranked on the device), and token alignment (a token label for
-every encoder frame from Whisper's cross-attention: the fused z-score / median / head-mean cost and dynamic time warping).  Mirrors the names of the reference's ``whisper_sae.analysis.feature_viz``
+every encoder frame from Whisper's cross-attention: the fused z-score / median / head-mean cost and dynamic time warping), and
+audio clip export (the clips a feature fires on, cut, peak-normalised, faded and converted to 16-bit PCM for all features in
+one launch over a device-resident waveform bank, written as WAV files with a manifest, and per-feature reports).  Mirrors the names of the reference's ``whisper_sae.analysis.feature_viz``
 that sit on that path."""
 
 from .alignment import (CrossAttentionTap, FrameAlignment, RawAlignment, align_tokens, align_weights, aligned_batches,
                         alignment_heads)
+from .audio_extraction import (AudioClipConfig, AudioClipExtractor, ClipBatch, WaveformBank, clip_table_for_activations,
+                               clip_table_for_events, create_indexed_audio_loader, cut_clips, read_wav, write_wav)
 from .clustering import (ClusterScores, CodeKMeans, IterationStats, cluster_scores, collect_code_clusters,
                          unit_sequences)
 from .coactivation import (CoactivationNeighbors, CoactivationTracker, collect_coactivation,
@@ -26,7 +30,7 @@ from .dictionary import NearestFeatures, compare_dictionaries, duplicate_feature
 from .discrimination import AbxItems, AbxScores, collect_abx, items_from_labels, segment_distances
 from .dynamics import (BoundaryCurve, BoundaryScorer, CodeDynamics, DynamicsSummary, LagStats, boundaries_from_labels,
                        boundary_curve, collect_code_dynamics, detect_boundaries, frame_similarity, novelty)
-from .feature_viz import FeatureActivation, TopKTracker, collect_top_activations
+from .feature_viz import FeatureActivation, FeatureInterpretation, FeatureReport, TopKTracker, collect_top_activations
 from .group_stats import (GroupEffects, SegmentPooler, bootstrap_weights, collect_pooled, group_effect_sizes,
                           top_group_features)
 from .labels import (BestLabels, LabelAssociation, LabelScores, automated_labels, best_labels, collect_label_association,
@@ -58,4 +62,6 @@ __all__ = ["FeatureActivation", "TopKTracker", "collect_top_activations", "Neare
            "IterationStats", "cluster_scores", "collect_code_clusters", "unit_sequences", "AbxItems", "AbxScores", "collect_abx",
            "items_from_labels", "segment_distances", "PairExport", "TokenAssociation", "TopPairs", "collect_token_association",
            "CrossAttentionTap", "FrameAlignment", "RawAlignment", "align_tokens", "align_weights", "aligned_batches",
-           "alignment_heads"]
+           "alignment_heads", "AudioClipConfig", "AudioClipExtractor", "ClipBatch", "WaveformBank", "clip_table_for_activations",
+           "clip_table_for_events", "create_indexed_audio_loader", "cut_clips", "read_wav", "write_wav", "FeatureInterpretation",
+           "FeatureReport"]

@@ -297,6 +297,78 @@ class TopKTracker:
         return t
 
 
+@dataclass
+class FeatureInterpretation:
+    """What a feature is taken to represent (the reference's fields and dict form).  ``category``: "phoneme", "prosody",
+    "speaker", "semantic", "unknown" ...; ``confidence`` in [0, 1]; ``automated_labels`` takes the dict that
+    ``labels.automated_labels`` returns for the feature."""
+
+    feature_idx: int
+    category: str
+    description: str
+    confidence: float
+    evidence: list = field(default_factory=list)
+    automated_labels: dict = field(default_factory=dict)
+
+    def to_dict(self) -> dict:
+        return {"feature_idx": self.feature_idx, "category": self.category, "description": self.description,
+                "confidence": self.confidence, "evidence": self.evidence, "automated_labels": self.automated_labels}
+
+
+class FeatureReport:
+    """Per-feature and summary reports of a tracker as dicts and JSON files (the reference's methods and forms).  Host only.
+
+    ``clips``: an ``AudioClipExtractor`` of the same tracker (optional).  The tracker builds its examples anew on every
+    read, so the paths of the clips live in the extractor's lists; with ``clips`` the reports read those."""
+
+    def __init__(self, tracker: TopKTracker, output_dir, *, clips=None):
+        self.tracker = tracker
+        self.output_dir = Path(output_dir)
+        self.output_dir.mkdir(parents=True, exist_ok=True)
+        self.clips = clips
+        self.interpretations: dict = {}
+
+    def generate_feature_report(self, feature_idx: int, include_audio_paths: bool = True) -> dict:
+        examples = self.clips.examples(feature_idx) if self.clips is not None else self.tracker.get_top_examples(feature_idx)
+        report = {"feature_idx": feature_idx, "stats": self.tracker.get_feature_stats()[feature_idx], "top_examples": []}
+        for ex in examples:
+            entry = {"activation_value": ex.activation_value, "sample_idx": ex.sample_idx, "position_idx": ex.position_idx,
+                     "timestamp_ms": ex.timestamp_ms, "transcription": ex.transcription}
+            if include_audio_paths and ex.audio_path:
+                entry["audio_path"] = ex.audio_path
+            report["top_examples"].append(entry)
+        if feature_idx in self.interpretations:
+            report["interpretation"] = self.interpretations[feature_idx].to_dict()
+        return report
+
+    def generate_summary_report(self, top_n: int = 100) -> dict:
+        """The ``top_n`` features by their largest activation (a stable sort: ties keep the feature order)."""
+        ranked = sorted(self.tracker.get_feature_stats().items(), key=lambda item: item[1]["max_activation"],
+                        reverse=True)[:top_n]
+        return {"num_features": self.tracker.num_features, "samples_processed": self.tracker.samples_processed,
+                "total_activations": self.tracker.total_activations,
+                "top_features": [{"feature_idx": f, **stats} for f, stats in ranked]}
+
+    def save_reports(self, top_n: int = 100) -> None:
+        """``summary.json``, ``features/feature_{idx:05d}.json`` for the summary's features, ``tracker_state.json``."""
+        summary = self.generate_summary_report(top_n=top_n)
+        with open(self.output_dir / "summary.json", "w") as fh:
+            json.dump(summary, fh, indent=2)
+        features_dir = self.output_dir / "features"
+        features_dir.mkdir(exist_ok=True)
+        for entry in summary["top_features"]:
+            f = entry["feature_idx"]
+            with open(features_dir / f"feature_{f:05d}.json", "w") as fh:
+                json.dump(self.generate_feature_report(f), fh, indent=2)
+        self.tracker.save(self.output_dir / "tracker_state.json")
+
+    def add_interpretation(self, feature_idx: int, category: str, description: str, confidence: float = 0.5,
+                           evidence: Optional[list] = None, automated_labels: Optional[dict] = None) -> None:
+        self.interpretations[feature_idx] = FeatureInterpretation(
+            feature_idx=feature_idx, category=category, description=description, confidence=confidence,
+            evidence=evidence or [], automated_labels=automated_labels or {})
+
+
 def collect_top_activations(model: torch.nn.Module, dataloader, num_features: int, k: int = 20,
                             device: str = "cuda") -> TopKTracker:
     """Top-k activating examples over a dataset (reference feature_viz.py:425-484).  A model with
