@@ -1232,7 +1232,7 @@ int wsae_align_dtw(const float* cost, int32_t n_utt, int64_t ld_t, int64_t ld_f,
  * with 64-byte alignment and multiples of 16; any other alignment is served by 4-byte stores of the same values.
  * Workspace (4-byte aligned): wsae_logmel_workspace_bytes(n_utt, n_samples, n_mels) - one maximum per 64 frames; -1 for
  * invalid arguments; contents arbitrary on entry.  n_utt == 0 returns WSAE_OK and touches nothing. */
-#define WSAE_DT_I16 3 /* wsae_logmel and wsae_clip_extract only */
+#define WSAE_DT_I16 3 /* wsae_logmel, wsae_clip_extract and wsae_resample only */
 #define WSAE_LOGMEL_NFFT 400
 #define WSAE_LOGMEL_HOP 160
 #define WSAE_LOGMEL_BINS 201
@@ -1283,6 +1283,51 @@ int wsae_clip_extract(const void* x, int32_t x_dtype, int32_t n_utt, int64_t ld_
                       int64_t max_count, const int64_t* clip_off, int32_t gain_mode, float target, int32_t fade, void* out,
                       int32_t out_dtype, int64_t out_elems, int32_t* out_len, float* out_peak, void* workspace,
                       int64_t workspace_bytes, void* stream);
+
+/* ---- resampling: downmix, polyphase FIR, lengths and PCM conversion ---------------------------------
+ * Interleaved waveforms at one rate in, mono waveforms at another out, as one kernel.  Ctx-free; the caller's stream, no
+ * allocation, no host synchronisation, no atomics, no workspace; argument errors are found on the host before any HIP call.
+ * An utterance's output depends on that utterance's samples and the tables alone: not on its row, the other rows, the tile
+ * or the alignment of either side.  tests/resample_oracle.py restates all of this in numpy.
+ *
+ * Input.  x [n_utt] rows of stride ld_x (elements) of x_dtype WSAE_DT_F32 or WSAE_DT_I16 (int16 is scaled by 2^-15: exact).
+ * Frames are interleaved: sample m of channel c of utterance u is x[u ld_x + m channels + c] (what `wave` and `soundfile`
+ * give); 1 <= channels <= WSAE_RESAMPLE_MAX_CHANNELS = 8.  length int32 [n_utt] in DEVICE memory, counted in frames:
+ * L_u = min(max(length[u], 0), max_length), and nothing of x at or beyond frame L_u is read.  max_length (host) bounds the
+ * lengths: 0 <= max_length < 2^31, max_length channels <= ld_x.  Samples must be finite.
+ * Downmix, float32, once, before the filter: channels == 1: mono[m] = x[m].  Otherwise s = x[m][0]; s = fl(s + x[m][c]) for
+ * c = 1 .. channels - 1 in this order; mono[m] = fl(s / float(channels)), an IEEE division.
+ * Filter.  orig and new_ (the two rates divided by their gcd) lie in 1 .. WSAE_RESAMPLE_MAX_RATE = 1024 and are coprime.
+ * taps fp32 [new_][n_taps] row-major and first int32 [new_], both in device memory; 1 <= n_taps <= WSAE_RESAMPLE_MAX_TAPS =
+ * 512.  halo (host, 0 .. WSAE_RESAMPLE_MAX_HALO = 4096, n_taps <= orig + 2 halo) is the caller's promise that -halo <=
+ * first[p] and first[p] + n_taps <= orig + halo for every p; a first[p] that breaks it is clamped into that range, so that no
+ * access leaves the staged span, and the values of that phase are then unspecified.  With xz[m] = mono[m] for 0 <= m < L_u
+ * and 0 elsewhere, and j = i new_ + p (0 <= p < new_):
+ *   y[j] = ONE chain acc = fmaf(xz[i orig + first[p] + w], taps[p][w], acc) from acc = +0 over w = 0, 1, .. n_taps - 1 in
+ * this order; padding taps (zeros) take part like any other.
+ * Lengths.  out_len int32 [n_utt] in device memory: ceil(new_ L_u / orig), computed in int64 (torchaudio's target_length).
+ * Every cell j < out_cols (host) of a row is written: y[j] for j < out_len[u], zero for the rest; cells at or beyond
+ * out_cols and anything behind the last row stay untouched.  ceil(new_ max_length / orig) <= out_cols <= ld_y, out_cols < 2^31.
+ * Output.  out [n_utt] rows of stride ld_y (elements).  out_dtype WSAE_DT_F32: y[j].  WSAE_DT_I16: clamp(rintf(fl(y[j] *
+ * 32768)), -32768, 32767), round half to even - the inverse of the scaling on the way in (NOT the 32767 of the clip writer,
+ * which follows the WAV convention).  x and out are aligned to their elements; any ld_x, ld_y and base are served: the bulk
+ * of a row's tile leaves as 16-byte stores from its first 64-byte boundary on, write-through, the ends elementwise, same
+ * values; mono and stereo rows whose frames meet the 16-byte boundaries are read 16 bytes wide, all others by element.
+ * Identity.  orig = new_ = 1, taps = [[1.0f]], first = [0], halo = 0: fmaf(x, 1, +0) = x for every finite x up to the sign of
+ * a zero; the downmix and both conversions are still served.
+ * Geometry.  A workgroup owns WSAE_RESAMPLE_TILE consecutive outputs of an utterance and holds their input span, the
+ * tap table and the converted outputs in at most WSAE_RESAMPLE_LDS_BYTES of LDS; the tile is halved until the span fits, and
+ * a table that does not fit beside it is read through the cache.  (Within the limits above one block always fits.)
+ * n_utt == 0 returns WSAE_OK and touches nothing. */
+#define WSAE_RESAMPLE_TILE 1024 /* outputs per workgroup */
+#define WSAE_RESAMPLE_LDS_BYTES 65536
+#define WSAE_RESAMPLE_MAX_CHANNELS 8
+#define WSAE_RESAMPLE_MAX_RATE 1024
+#define WSAE_RESAMPLE_MAX_TAPS 512
+#define WSAE_RESAMPLE_MAX_HALO 4096
+int wsae_resample(const void* x, int32_t x_dtype, int32_t n_utt, int64_t ld_x, int32_t channels, const int32_t* length,
+                  int64_t max_length, int32_t orig, int32_t new_, const float* taps, const int32_t* first, int32_t n_taps,
+                  int32_t halo, void* out, int32_t out_dtype, int64_t ld_y, int64_t out_cols, int32_t* out_len, void* stream);
 
 #ifdef __cplusplus
 }

@@ -10,8 +10,10 @@ What differs:
   seeded random-init model of the configured geometry (``--whisper-random-init``: smoke runs and tests) - never a
   hub name: this build downloads nothing.  ``run()`` also takes a model OBJECT;
 * the mel features come from a tensor file (``--mel``: ``torch.save``d ``[N, n_mels, frames]``), are synthetic
-  (``--synthetic-mel N``), or are computed on the device from waveforms (``--audio FILE``, ``--synthetic-audio N``);
-  decoding audio files and the LibriSpeech loader stay outside this build;
+  (``--synthetic-mel N``), or are computed on the device from waveforms (``--audio FILE``, ``--wav PATH ...``,
+  ``--synthetic-audio N``) of any sample rate and channel count: the resampler to 16 kHz mono and the log-mel front end
+  run there.  ``--wav`` reads 16-bit PCM WAV files; decoding other audio formats and the LibriSpeech loader stay
+  outside this build;
 * ``--stream-to-ring``: extraction pushes the layer-normed activations straight into the on-device ring the trainer
   samples from (one kernel per hooked call) - no ``.cpu()``, no cache file, no reload (SURVEY.md row N2);
 * cached activations are loaded once into the on-device ring buffer and batches are drawn there;
@@ -58,8 +60,11 @@ def parse_args(argv=None):
     ap.add_argument("--synthetic-mel", type=int, default=0, metavar="N", help="extract from N synthetic mel clips")
     ap.add_argument("--mel-frames", type=int, default=3000, help="frames per synthetic clip (3000 = 30 s)")
     ap.add_argument("--audio", type=str, default=None,
-                    help="torch.save'd waveforms at 16 kHz to extract from: a [N, samples] tensor (float32 or int16), or a dict "
-                         "with 'waveforms' and 'lengths'; the log-mel front end runs on the device")
+                    help="torch.save'd waveforms to extract from: a [N, samples] tensor at 16 kHz (float32 or int16), or a dict "
+                         "with 'waveforms' ([N, samples] or [N, samples, channels]), 'lengths' and 'sample_rate' (default "
+                         "16000); resampling and the log-mel front end run on the device")
+    ap.add_argument("--wav", type=str, nargs="+", default=None, metavar="PATH",
+                    help="16-bit PCM WAV files to extract from, of any sample rate and channel count")
     ap.add_argument("--synthetic-audio", type=int, default=0, metavar="N",
                     help="extract from N synthetic waveforms (seeded noise plus tones, lengths varied)")
     ap.add_argument("--stream-to-ring", action="store_true",
@@ -110,10 +115,10 @@ def mel_batches(cfg: ExperimentConfig, args, model, batch_size: int = 16):
     elif args.synthetic_mel:
         g = torch.Generator().manual_seed(cfg.training.seed)
         mel = torch.randn(args.synthetic_mel, model.config.num_mel_bins, args.mel_frames, generator=g)
-    elif args.audio or args.synthetic_audio:
+    elif args.audio or args.wav or args.synthetic_audio:
         return audio_batches(cfg, args, model, batch_size)
     else:
-        raise SystemExit("extraction needs mel features: --mel FILE or --synthetic-mel N (audio decoding is outside this build)")
+        raise SystemExit("extraction needs mel features or waveforms: --mel FILE, --synthetic-mel N, --audio FILE or --wav PATH ...")
     return [mel[i:i + batch_size] for i in range(0, mel.shape[0], batch_size)]
 
 
@@ -130,22 +135,51 @@ def synthetic_audio(n: int, samples: int, seed: int):
     return wave, lengths.to(torch.int32)
 
 
+def wav_batches(paths, n_mels: int, device, samples: int, mel_frames: int, batch_size: int = 16):
+    """``--wav``: the files grouped by (sample rate, channels), each group through its own ``AudioFrontEnd`` in batches."""
+    from whisper_sae.analysis.audio_extraction import read_wav
+    from whisper_sae.data import AudioFrontEnd, resampled_length
+
+    groups = {}
+    for path in paths:
+        wave, rate = read_wav(path, return_rate=True, mono=False)
+        if resampled_length(wave.shape[0], rate) > samples:
+            raise SystemExit(f"--wav: {wave.shape[0]} samples per clip exceed --mel-frames {mel_frames} x 160")
+        groups.setdefault((rate, tuple(wave.shape[1:])), []).append(wave)
+    out = []
+    for (rate, _), waves in groups.items():
+        frontend = AudioFrontEnd(rate, n_mels, device=device, n_samples=samples)
+        for i in range(0, len(waves), batch_size):
+            out.append(frontend([w.to(device) for w in waves[i:i + batch_size]]))
+    return out
+
+
 def audio_batches(cfg: ExperimentConfig, args, model, batch_size: int = 16):
-    """``mel_batches`` from waveforms: ``LogMel`` turns every batch into ``[B, n_mels, --mel-frames]`` on the model's device."""
-    from whisper_sae.data import LogMel
+    """``mel_batches`` from waveforms: ``LogMel`` turns every batch into ``[B, n_mels, --mel-frames]`` on the model's device,
+    behind the resampler (``AudioFrontEnd``) where the waveforms are not 16 kHz mono."""
+    from whisper_sae.data import AudioFrontEnd, LogMel, resampled_length
 
     samples = args.mel_frames * 160
+    device = next(model.parameters()).device
+    rate = 16000
+    if args.wav:
+        return wav_batches(args.wav, model.config.num_mel_bins, device, samples, args.mel_frames, batch_size)
     if args.audio:
         held = torch.load(args.audio, weights_only=True)
         wave, lengths = (held["waveforms"], held.get("lengths")) if isinstance(held, dict) else (held, None)
-        if not isinstance(wave, torch.Tensor) or wave.ndim != 2:
-            raise SystemExit(f"--audio: expected [N, samples], got {tuple(getattr(wave, 'shape', ()))}")
-        if wave.shape[1] > samples:
+        has_rate = isinstance(held, dict) and "sample_rate" in held  # (without the key: 16 kHz mono, as before the resampler)
+        rate = int(held["sample_rate"]) if has_rate else rate
+        if not isinstance(wave, torch.Tensor) or wave.ndim not in ((2, 3) if has_rate else (2,)):
+            raise SystemExit(f"--audio: expected [N, samples]{' or [N, samples, channels]' if has_rate else ''}, got "
+                             f"{tuple(getattr(wave, 'shape', ()))}")
+        if resampled_length(wave.shape[1], rate) > samples:
             raise SystemExit(f"--audio: {wave.shape[1]} samples per clip exceed --mel-frames {args.mel_frames} x 160")
     else:
         wave, lengths = synthetic_audio(args.synthetic_audio, samples, cfg.training.seed)
-    device = next(model.parameters()).device
-    frontend = LogMel(model.config.num_mel_bins, device=device, n_samples=samples)
+    if rate == 16000 and wave.ndim == 2:
+        frontend = LogMel(model.config.num_mel_bins, device=device, n_samples=samples)
+    else:
+        frontend = AudioFrontEnd(rate, model.config.num_mel_bins, device=device, n_samples=samples)
     out = []
     for i in range(0, wave.shape[0], batch_size):
         part = None if lengths is None else torch.as_tensor(lengths)[i:i + batch_size]

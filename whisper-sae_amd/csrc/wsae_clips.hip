@@ -14,13 +14,15 @@
 //   (for_tile); the output begins at an arbitrary clip_off, so the image sits in LDS shifted by the elements that lead up to
 //   the output's first 64-byte boundary, and from that boundary on a lane stores 16 aligned bytes, a wave instruction whole
 //   64-byte pieces: those go write-through, the at most three vectors behind the last whole piece plain,
-//   the ragged ends elementwise.  The same values whatever the alignment.  The LDS writes of the staging are scalar (the
+//   the ragged ends elementwise (PcmTileStore, wsae_pcm.h: wsae_resample.hip stores the same way).  The same values
+//   whatever the alignment.  The LDS writes of the staging are scalar (the
 //   shift is arbitrary) and conflict 4- or 8-way; at 16 KB per tile that is a few hundred cycles against the thousands the
 //   tile's bytes take at the memory rate.
 // When neither the gain nor out_peak needs the peak (WSAE_CLIP_GAIN_NONE, out_peak null) the peak kernel is not launched.
 #include <math.h>
 
 #include "wsae_common.h"
+#include "wsae_pcm.h"
 
 // (x / m) * target * r is a division and two products, each rounded
 #pragma clang fp contract(off)
@@ -141,20 +143,11 @@ __global__ __launch_bounds__(CL_BLOCK) void clip_peak_kernel(ClipArgs a) {
     if (threadIdx.x == 0) a.tile_max[(int64_t)c * a.tiles + t] = mx;
 }
 
-template <int OT> struct ClipOut { typedef float type; };
-template <> struct ClipOut<WSAE_DT_I16> { typedef int16_t type; };
-
-template <int OT>
-__device__ __forceinline__ typename ClipOut<OT>::type clip_convert(float y, float scale) {
-    if constexpr (OT == WSAE_DT_I16) return (int16_t)(int)fminf(fmaxf(rintf(y * scale), -32768.0f), 32767.0f);
-    else return y;
-}
-
 template <int DT, int OT>
 __global__ __launch_bounds__(CL_BLOCK) void clip_write_kernel(ClipArgs a) {
-    typedef typename ClipOut<OT>::type T;
-    constexpr int VE = 16 / (int)sizeof(T), PIECE = 64 / (int)sizeof(T), PER = CL_TILE / VE / CL_BLOCK;
-    __shared__ __attribute__((aligned(64))) T s_y[CL_TILE + PIECE];
+    typedef typename PcmOut<OT>::type T;
+    typedef PcmTileStore<T, CL_TILE, CL_BLOCK> Store;
+    __shared__ __attribute__((aligned(64))) T s_y[CL_TILE + Store::PIECE];
     __shared__ float s_red[CL_WAVES];
     const int c = blockIdx.x / a.tiles, t = blockIdx.x % a.tiles, j0 = t * CL_TILE, tid = threadIdx.x;
     const ClipSpan s = clip_span(a, c);
@@ -172,11 +165,8 @@ __global__ __launch_bounds__(CL_BLOCK) void clip_write_kernel(ClipArgs a) {
     if (t >= tiles) return;
 
     const int mlen = min(CL_TILE, s.n - j0);
-    T* po = (T*)a.out + s.off + j0;
-    // lead: the cells in front of the output's first 64-byte boundary; cell j of the tile sits at s_y[j + shift], so that
-    // the cell on that boundary is at s_y[0] or s_y[PIECE]
-    const int lead = min((int)(((64 - ((uintptr_t)po & 63)) & 63) / sizeof(T)), mlen);
-    const int shift = (PIECE - lead) % PIECE;
+    const Store st((T*)a.out + s.off + j0, mlen);  // (wsae_pcm.h: cell j of the tile sits at s_y[j + shift])
+    const int shift = st.shift;
     const bool gain = a.gain_mode == WSAE_CLIP_GAIN_PEAK && m > 0.f;
     const float target = a.target, scale = a.scale, flen = (float)a.fade;
     const int fade = a.fade, last = s.n - 1;
@@ -186,23 +176,11 @@ __global__ __launch_bounds__(CL_BLOCK) void clip_write_kernel(ClipArgs a) {
             const int j = j0 + jl;
             y = y * ((float)min(min(j, last - j) + 1, fade) / flen);
         }
-        s_y[jl + shift] = clip_convert<OT>(y, scale);
+        s_y[jl + shift] = pcm_convert<OT>(y, scale);
     });
     __syncthreads();
 
-    if (tid < lead) po[tid] = s_y[tid + shift];
-    const int nvec = (mlen - lead) / VE, whole = nvec & ~3;  // whole: the vectors that make up whole 64-byte pieces
-    const float4* sv = (const float4*)(s_y + lead + shift);
-    T* pb = po + lead;
-    const __amdgpu_buffer_rsrc_t rs = wt_rsrc(pb);  // (based at the tile: the 32-bit offsets below stay under 16 KB)
-#pragma unroll
-    for (int k = 0; k < PER; ++k) {
-        const int v = tid + k * CL_BLOCK;
-        if (v < whole) wt_store4(rs, (int64_t)v * 16, sv[v]);
-        else if (v < nvec) *(float4*)(pb + v * VE) = sv[v];
-    }
-    const int done = lead + nvec * VE;
-    if (done + tid < mlen) po[done + tid] = s_y[done + tid + shift];
+    st.store(s_y);
 }
 
 inline bool dtype_ok(int dt) { return dt == WSAE_DT_F32 || dt == WSAE_DT_I16; }

@@ -38,9 +38,11 @@ PAIR_MAX_K, PAIR_MAX_TOKENS, PAIR_MAX_N, PAIR_BY_FEATURE, PAIR_BY_TOKEN = 128, 1
 PAIR_SCORES = ("count", "precision", "recall", "f1", "jaccard", "lift", "mean")  # WSAE_PAIR_COUNT .. WSAE_PAIR_MEAN, in order
 DT_F16 = 2  # wsae_align_cost only
 ALIGN_MAX_TOK, ALIGN_MAX_FRAMES, ALIGN_MAX_HEADS, ALIGN_MAX_WIDTH = 512, 2048, 32, 15  # wsae_align_cost / wsae_align_dtw
-DT_I16 = 3  # wsae_logmel and wsae_clip_extract only
+DT_I16 = 3  # wsae_logmel, wsae_clip_extract and wsae_resample only
 LOGMEL_NFFT, LOGMEL_HOP, LOGMEL_BINS, LOGMEL_COLS, LOGMEL_SIN_COL = 400, 160, 201, 416, 208  # wsae_logmel
 CLIP_TILE, CLIP_GAIN_NONE, CLIP_GAIN_PEAK = 4096, 0, 1  # wsae_clip_extract
+RESAMPLE_TILE, RESAMPLE_LDS_BYTES, RESAMPLE_MAX_CHANNELS = 1024, 65536, 8  # wsae_resample
+RESAMPLE_MAX_RATE, RESAMPLE_MAX_TAPS, RESAMPLE_MAX_HALO = 1024, 512, 4096
 BTK_STATE_WORDS = 8  # wsae_batch_topk_state: threshold, beta, last_t (f32), saturated_rows, kept, 3 reserved (i32)
 
 
@@ -190,6 +192,7 @@ SIGNATURES = {
     "wsae_clip_workspace_bytes": (_i64, [_i32, _i64]),
     "wsae_clip_extract": (C.c_int, [_p, _i32, _i32, _i64, _p, _i64, _i32, _p, _p, _p, _i64, _p, _i32, _f32, _i32, _p, _i32, _i64,
                                     _p, _p, _p, _i64, _p]),
+    "wsae_resample": (C.c_int, [_p, _i32, _i32, _i64, _i32, _p, _i64, _i32, _i32, _p, _p, _i32, _i32, _p, _i32, _i64, _i64, _p, _p]),
     "wsae_relu_needs_hidden":(C.c_int, [_p, _i32]),
     "wsae_relu_forward": (C.c_int, [_p, _p, _p, _i32, _p, _i32, _f32, _p, _p, _p, _p, _p]),
     "wsae_relu_backward": (C.c_int, [_p, _p, _p, _i32, _p, _i32, _f32, _p, _p, _p, _p]),

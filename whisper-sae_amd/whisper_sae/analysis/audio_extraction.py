@@ -249,28 +249,39 @@ def pcm16(samples) -> np.ndarray:
     return np.clip(scaled, -32768, 32767).astype(np.int16)
 
 
-def write_wav(path, samples, sample_rate: int = 16000) -> None:
-    """A mono 16-bit PCM WAV file through the standard library's ``wave``."""
-    sample_rate = int(sample_rate)
+def write_wav(path, samples, sample_rate: int = 16000, channels: int = 1) -> None:
+    """A 16-bit PCM WAV file through the standard library's ``wave``: mono, or with ``channels > 1`` the interleaved frames
+    ``samples [n, channels]``."""
+    sample_rate, channels = int(sample_rate), int(channels)
     if sample_rate < 1:
         raise ValueError(f"sample_rate must be positive, got {sample_rate}")
-    data = pcm16(samples)
+    if channels > 1:
+        a = samples.detach().cpu().numpy() if isinstance(samples, Tensor) else np.asarray(samples)
+        if a.ndim != 2 or a.shape[1] != channels:
+            raise ValueError(f"samples must be [n, {channels}], got shape {tuple(a.shape)}")
+        data = pcm16(a.reshape(-1))
+    else:
+        data = pcm16(samples)
     with wave.open(str(path), "wb") as fh:
-        fh.setnchannels(1)
+        fh.setnchannels(channels)
         fh.setsampwidth(2)
         fh.setframerate(sample_rate)
         fh.writeframes(data.astype("<i2", copy=False).tobytes())
 
 
-def read_wav(path, return_rate: bool = False):
+def read_wav(path, return_rate: bool = False, mono: bool = True):
     """A mono 16-bit PCM WAV file as a float32 tensor, samples scaled by 2^-15 (exact); with ``return_rate`` the pair
-    ``(samples, sample_rate)``."""
+    ``(samples, sample_rate)``.  With ``mono=False`` a file of several channels is read too, as interleaved frames
+    ``[n, channels]`` (what ``Resampler`` takes)."""
     with wave.open(str(path), "rb") as fh:
-        if fh.getnchannels() != 1 or fh.getsampwidth() != 2:
-            raise ValueError(f"{path}: need mono 16-bit PCM, got {fh.getnchannels()} channel(s) of {8 * fh.getsampwidth()} bits")
+        channels = fh.getnchannels()
+        if (mono and channels != 1) or fh.getsampwidth() != 2:
+            raise ValueError(f"{path}: need {'mono ' if mono else ''}16-bit PCM, got {channels} channel(s) of {8 * fh.getsampwidth()} bits")
         rate = fh.getframerate()
         raw = fh.readframes(fh.getnframes())
     samples = torch.from_numpy(np.frombuffer(raw, dtype="<i2").astype(np.float32) * np.float32(2.0 ** -15))
+    if channels > 1:
+        samples = samples.reshape(-1, channels)
     return (samples, rate) if return_rate else samples
 
 

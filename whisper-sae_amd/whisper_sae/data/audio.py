@@ -6,7 +6,8 @@ The arithmetic is fixed operation by operation in ``include/wsae.h``; ``tests/lo
 Framing follows the installed ``WhisperFeatureExtractor`` after its padding to ``n_samples``: a reflect pad of 200 samples
 around the padded signal, frames of 400 samples every 160, and no frame beyond ``n_samples / 160``.
 
-Out of scope: decoding audio files, resampling, dithering, other ``n_fft`` / hop values, chunking of recordings longer than
+Other rates and channel counts go through ``Resampler`` / ``AudioFrontEnd`` (``resample.py``) first.  Out of scope: decoding
+audio files other than 16-bit PCM WAV, dithering, other ``n_fft`` / hop values, chunking of recordings longer than
 ``n_samples``.  There is no CPU path.
 """
 
@@ -231,17 +232,19 @@ def log_mel_spectrogram(waveforms, lengths=None, *, n_mels: int = 80, device=Non
 def features_from_batch(frontend: Optional[LogMel], batch):
     """What ``extract_and_cache_features(frontend=...)`` and ``aligned_batches(frontend=...)`` do to the first item of a
     batch: a 2-D tensor is a batch of waveforms and is converted, with the second item of a tuple / list as its lengths;
-    a 3-D tensor is mel features already and passes through, as does everything when there is no front end."""
+    a 3-D tensor is mel features already and passes through, as does everything when there is no front end.  An
+    ``AudioFrontEnd`` also converts the 3-D tensors that are interleaved waveforms ``[n_utt, S, C]`` (its ``is_waveform``)."""
     if frontend is None:
         return batch[0] if isinstance(batch, (list, tuple)) else batch
-    if isinstance(batch, (list, tuple)):
-        first = batch[0]
-        if isinstance(first, Tensor) and first.dim() == 2:
-            return frontend(first, batch[1] if len(batch) > 1 else None)
+    from .resample import AudioFrontEnd
+    first = batch[0] if isinstance(batch, (list, tuple)) else batch
+    if isinstance(frontend, AudioFrontEnd):
+        wave = frontend.is_waveform(first)
+    else:
+        wave = isinstance(first, Tensor) and first.dim() == 2
+    if not wave:
         return first
-    if isinstance(batch, Tensor) and batch.dim() == 2:
-        return frontend(batch)
-    return batch
+    return frontend(first, batch[1] if isinstance(batch, (list, tuple)) and len(batch) > 1 else None)
 
 
 __all__ = ["LogMel", "dft_basis", "frame_of_sample", "hann_window", "log_mel_spectrogram", "mel_filter_bank",
