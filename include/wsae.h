@@ -1230,6 +1230,7 @@ int wsae_align_dtw(const float* cost, int32_t n_utt, int64_t ld_t, int64_t ld_f,
  * encoder takes.  Only the cells (u, m, t < T) are written.  mel_power (nullable), same strides: mel[t][m] before floor and
  * log.  With out, mel_power 16-byte aligned and ld_m, ld_u multiples of 4 the stores are 16 bytes wide, and write-through
  * with 64-byte alignment and multiples of 16; any other alignment is served by 4-byte stores of the same values.
+ * x and out are aligned to their elements (2 bytes for int16 x, else 4): anything else is WSAE_ERR_INVALID.
  * Workspace (4-byte aligned): wsae_logmel_workspace_bytes(n_utt, n_samples, n_mels) - one maximum per 64 frames; -1 for
  * invalid arguments; contents arbitrary on entry.  n_utt == 0 returns WSAE_OK and touches nothing. */
 #define WSAE_DT_I16 3 /* wsae_logmel, wsae_clip_extract and wsae_resample only */

@@ -213,6 +213,14 @@ def test_logmel_on_ragged_lists_views_and_errors():
         fe([torch.zeros(4, device=DEV), torch.zeros(2, 2, device=DEV)])
     with pytest.raises(ValueError, match=r"out must be float32 \[2, 80, 100\]"):
         fe(torch.zeros(2, 480, device=DEV), out=torch.zeros(2, 80, 99, device=DEV))
+    # the C entry point refuses a float32 x that is not aligned to its element, before anything is launched
+    x, n, out = torch.zeros(P + 1, device=DEV), torch.full((1,), P, dtype=torch.int32, device=DEV), torch.empty(1, 80, 100, device=DEV)
+    need = N.lib().wsae_logmel_workspace_bytes(1, P, 80)
+    ws = torch.empty(need, dtype=torch.uint8, device=DEV)
+    with pytest.raises(N.WsaeError, match="aligned to"):
+        N.check(N.lib().wsae_logmel(x.data_ptr() + 2, N.DT_F32, 1, P, n.data_ptr(), P, P, fe.basis.data_ptr(), fe.filters.data_ptr(), 80,
+                                    out.data_ptr(), 100, 8000, None, ws.data_ptr(), need, torch.cuda.current_stream().cuda_stream),
+                "wsae_logmel")
 
 
 def test_extraction_from_waveforms_equals_extraction_from_their_mel():

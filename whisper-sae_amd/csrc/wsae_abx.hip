@@ -362,8 +362,8 @@ extern "C" int wsae_dtw_matrix(const float* vals, const int32_t* idx, int32_t k,
     if (n_a == 0 || n_b == 0 || n_rows == 0) return WSAE_OK;
     WSAE_REQUIRE(vals && idx && a_start && a_len && b_start && b_len && dist, "wsae_dtw_matrix: null pointer");
     const DynLayout w = dyn_layout(n_rows, k);
-    CW_REQUIRE_WORKSPACE("wsae_dtw_matrix", workspace, workspace_bytes, w.total, n_rows);
-    CW_REQUIRE_ALIGNED8("wsae_dtw_matrix", workspace);
+    WSAE_REQUIRE_WORKSPACE("wsae_dtw_matrix", workspace, workspace_bytes, w.total, n_rows);
+    WSAE_REQUIRE_WORKSPACE_ALIGNED("wsae_dtw_matrix", workspace, 8);
     char* ws = (char*)workspace;
     hipStream_t st = (hipStream_t)stream;
     DynArgs c = {};
@@ -408,8 +408,8 @@ extern "C" int wsae_abx_count(const float* dist, int64_t ldd, int32_t x_lo, int3
     WSAE_REQUIRE(dist && cat && wins2 && total && skipped, "wsae_abx_count: null pointer");
     WSAE_REQUIRE(spk || mode == WSAE_ABX_ANY, "wsae_abx_count: WSAE_ABX_WITHIN and WSAE_ABX_ACROSS need spk (null pointer)");
     const int64_t need = align256(4 * (int64_t)n_items * n_x);
-    CW_REQUIRE_WORKSPACE("wsae_abx_count", workspace, workspace_bytes, need, n_x);
-    CW_REQUIRE_ALIGNED8("wsae_abx_count", workspace);
+    WSAE_REQUIRE_WORKSPACE("wsae_abx_count", workspace, workspace_bytes, need, n_x);
+    WSAE_REQUIRE_WORKSPACE_ALIGNED("wsae_abx_count", workspace, 8);
     AbxArgs a = {};
     a.dist = dist, a.ldd = ldd, a.x_lo = x_lo, a.n_x = n_x, a.n_items = n_items, a.n_cats = n_cats, a.mode = mode;
     a.cat = cat, a.ctx = ctx, a.spk = mode == WSAE_ABX_ANY ? nullptr : spk;

@@ -420,8 +420,8 @@ extern "C" int wsae_align_dtw(const float* cost, int32_t n_utt, int64_t ld_t, in
     WSAE_REQUIRE(ld_ok(ld_t) && ld_ok(ld_f), "wsae_align_dtw: need 1 <= ld_t, ld_f <= %lld (got %lld, %lld)", (long long)AL_MAX_LD,
                  (long long)ld_t, (long long)ld_f);
     const int64_t need = wsae_align_workspace_bytes(n_utt, ld_t, ld_f);
-    CW_REQUIRE_WORKSPACE("wsae_align_dtw", workspace, workspace_bytes, need, n_utt);
-    CW_REQUIRE_ALIGNED8("wsae_align_dtw", workspace);
+    WSAE_REQUIRE_WORKSPACE("wsae_align_dtw", workspace, workspace_bytes, need, n_utt);
+    WSAE_REQUIRE_WORKSPACE_ALIGNED("wsae_align_dtw", workspace, 8);
     if (n_utt == 0) return WSAE_OK;
     DtwArgs a = {cost,      ld_t,    ld_f,      row_first, row_count, n_frames, n_bad, frame_pos, tok_start,
                  tok_end,   path_cost, path_len, (unsigned long long*)status, (uint32_t*)workspace};

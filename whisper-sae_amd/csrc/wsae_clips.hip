@@ -74,61 +74,12 @@ __device__ __forceinline__ ClipSpan clip_span(const ClipArgs& a, int c) {
     return s;
 }
 
-// f(j, x_j) for every j in [0, m) exactly once, x_j = element first + j of x as float: scalar loads up to the first 16-byte
-// boundary, one 16-byte load per lane from there (all of a thread's loads issue before the first use), scalar loads behind
-// the last whole vector.  Nothing outside [first, first + m) is read.  m <= CL_TILE.
+// f(j, x_j) for every j in [0, m) exactly once, x_j = element first + j of x as float (pcm_for_span, wsae_pcm.h: nothing
+// outside [first, first + m) is read).  m <= CL_TILE, so its batch of 16-byte loads is the only one.
 template <int DT, class F>
 __device__ __forceinline__ void for_tile(const void* x, int64_t first, int m, F&& f) {
-    typedef short short8 __attribute__((ext_vector_type(8)));
-    constexpr int VE = DT == WSAE_DT_I16 ? 8 : 4, ES = 16 / VE, PER = CL_TILE / VE / CL_BLOCK;
-    const char* p = (const char*)x + first * ES;
-    const int lead = min((int)(((16 - ((uintptr_t)p & 15)) & 15) / ES), m);
-    const int nvec = (m - lead) / VE, done = lead + nvec * VE;
-    auto one = [&](int j) -> float {
-        if constexpr (DT == WSAE_DT_I16) return (float)((const int16_t*)p)[j] * 0x1p-15f;
-        else return ((const float*)p)[j];
-    };
-    const int tid = threadIdx.x;
-    if constexpr (DT == WSAE_DT_I16) {
-        const short8* pv = (const short8*)(p + lead * ES);
-        short8 q[PER];
-#pragma unroll
-        for (int k = 0; k < PER; ++k)
-            if (tid + k * CL_BLOCK < nvec) q[k] = pv[tid + k * CL_BLOCK];
-        if (tid < lead) f(tid, one(tid));
-#pragma unroll
-        for (int k = 0; k < PER; ++k) {
-            const int v = tid + k * CL_BLOCK;
-            if (v < nvec) {
-#pragma unroll
-                for (int i = 0; i < VE; ++i) f(lead + v * VE + i, (float)q[k][i] * 0x1p-15f);
-            }
-        }
-    } else {
-        const f32x4* pv = (const f32x4*)(p + lead * ES);
-        f32x4 q[PER];
-#pragma unroll
-        for (int k = 0; k < PER; ++k)
-            if (tid + k * CL_BLOCK < nvec) q[k] = pv[tid + k * CL_BLOCK];
-        if (tid < lead) f(tid, one(tid));
-#pragma unroll
-        for (int k = 0; k < PER; ++k) {
-            const int v = tid + k * CL_BLOCK;
-            if (v < nvec) {
-#pragma unroll
-                for (int i = 0; i < VE; ++i) f(lead + v * VE + i, q[k][i]);
-            }
-        }
-    }
-    if (done + tid < m) f(done + tid, one(done + tid));  // (fewer than VE of them)
-}
-
-// the maximum of one value per thread, in every thread
-__device__ __forceinline__ float block_max(float v, float* s_red) {
-    v = wave_max(v);
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3]));
+    typedef PcmIn<DT> In;
+    pcm_for_span<DT, 1, CL_BLOCK, CL_TILE / In::VE / CL_BLOCK>((const typename In::elem*)x + first, m, f);
 }
 
 template <int DT>
@@ -183,7 +134,6 @@ __global__ __launch_bounds__(CL_BLOCK) void clip_write_kernel(ClipArgs a) {
     st.store(s_y);
 }
 
-inline bool dtype_ok(int dt) { return dt == WSAE_DT_F32 || dt == WSAE_DT_I16; }
 inline int64_t clip_tiles(int64_t max_count) { return max_count > CL_TILE ? ceil_div64(max_count, CL_TILE) : 1; }
 
 template <int DT>
@@ -205,29 +155,25 @@ extern "C" int wsae_clip_extract(const void* x, int32_t x_dtype, int32_t n_utt, 
                                  float target, int32_t fade, void* out, int32_t out_dtype, int64_t out_elems, int32_t* out_len,
                                  float* out_peak, void* workspace, int64_t workspace_bytes, void* stream) {
     WSAE_REQUIRE(x && length && clip_utt && clip_start && clip_count && clip_off && out && out_len, "wsae_clip_extract: null pointer");
-    WSAE_REQUIRE(dtype_ok(x_dtype), "wsae_clip_extract: unknown x_dtype %d (float32 or int16)", x_dtype);
-    WSAE_REQUIRE(dtype_ok(out_dtype), "wsae_clip_extract: unknown out_dtype %d (float32 or int16)", out_dtype);
-    WSAE_REQUIRE(n_utt >= 0, "wsae_clip_extract: n_utt must not be negative (got %d)", n_utt);
+    PCM_REQUIRE_DTYPE("wsae_clip_extract", x_dtype);
+    PCM_REQUIRE_DTYPE("wsae_clip_extract", out_dtype);
+    PCM_REQUIRE_N_UTT("wsae_clip_extract", n_utt);
     WSAE_REQUIRE(n_clips >= 0, "wsae_clip_extract: n_clips must not be negative (got %d)", n_clips);
     WSAE_REQUIRE(max_count >= 0 && max_count <= CL_MAX_COUNT, "wsae_clip_extract: need 0 <= max_count <= %lld (got %lld)",
                  (long long)CL_MAX_COUNT, (long long)max_count);
-    WSAE_REQUIRE(max_length >= 0 && max_length <= 0x7fffffffll, "wsae_clip_extract: need 0 <= max_length < 2^31 (got %lld)",
-                 (long long)max_length);
-    WSAE_REQUIRE(ld_x >= max_length, "wsae_clip_extract: ld_x %lld is below max_length %lld", (long long)ld_x, (long long)max_length);
+    PCM_REQUIRE_MAX_LENGTH("wsae_clip_extract", max_length);
+    PCM_REQUIRE_LD_X("wsae_clip_extract", ld_x, max_length, "max_length");
     WSAE_REQUIRE(out_elems >= 0, "wsae_clip_extract: out_elems must not be negative (got %lld)", (long long)out_elems);
     WSAE_REQUIRE(gain_mode == WSAE_CLIP_GAIN_NONE || gain_mode == WSAE_CLIP_GAIN_PEAK, "wsae_clip_extract: unknown gain_mode %d",
                  gain_mode);
     WSAE_REQUIRE(isfinite(target), "wsae_clip_extract: target must be finite");
     WSAE_REQUIRE(fade >= 0, "wsae_clip_extract: fade must not be negative (got %d)", fade);
-    const uintptr_t xa = x_dtype == WSAE_DT_I16 ? 1 : 3, oa = out_dtype == WSAE_DT_I16 ? 1 : 3;
-    WSAE_REQUIRE(((uintptr_t)x & xa) == 0 && ((uintptr_t)out & oa) == 0, "wsae_clip_extract: x and out must be aligned to their elements");
-    WSAE_REQUIRE((((uintptr_t)length | (uintptr_t)clip_utt | (uintptr_t)clip_count | (uintptr_t)out_len | (uintptr_t)out_peak) & 3) == 0 &&
-                     (((uintptr_t)clip_start | (uintptr_t)clip_off) & 7) == 0,
-                 "wsae_clip_extract: the int32 / float tables must be 4-byte aligned, clip_start and clip_off 8-byte");
+    PCM_REQUIRE_ELEMENTS_ALIGNED("wsae_clip_extract", x, x_dtype, out, out_dtype);
+    PCM_REQUIRE_TABLES_ALIGNED("wsae_clip_extract", ptr_bits(length, clip_utt, clip_count, out_len, out_peak), ptr_bits(clip_start, clip_off),
+                               "the int32 / float tables must be 4-byte aligned, clip_start and clip_off 8-byte");
     const int64_t need = wsae_clip_workspace_bytes(n_clips, max_count);
-    WSAE_REQUIRE(workspace_bytes >= need && (workspace || n_clips == 0), "wsae_clip_extract: workspace too small (%lld < %lld)",
-                 (long long)(workspace ? workspace_bytes : 0), (long long)need);
-    WSAE_REQUIRE(((uintptr_t)workspace & 3) == 0, "wsae_clip_extract: the workspace must be 4-byte aligned");
+    WSAE_REQUIRE_WORKSPACE("wsae_clip_extract", workspace, workspace_bytes, need, n_clips);
+    WSAE_REQUIRE_WORKSPACE_ALIGNED("wsae_clip_extract", workspace, 4);
     const int64_t tiles = clip_tiles(max_count);
     WSAE_REQUIRE((int64_t)n_clips * tiles <= 0x7fffffffll, "wsae_clip_extract: n_clips * tiles of max_count is too large for one launch");
     if (n_clips == 0) return WSAE_OK;

@@ -168,11 +168,6 @@ inline bool lag_ok(int lag) { return lag >= -1024 && lag <= 1024; }
 #define CW_REQUIRE_LISTS(FN, cap, t_row, t_val)                                                                           \
     WSAE_REQUIRE((cap) >= 0 && (((t_row) && (t_val)) || (cap) == 0), FN ": cap %lld entries need t_row and t_val",        \
                  (long long)(cap))
-// need bytes of workspace; no rows need none, a null workspace counts as 0 bytes
-#define CW_REQUIRE_WORKSPACE(FN, workspace, workspace_bytes, need, n_rows)                                                \
-    WSAE_REQUIRE((workspace_bytes) >= (need) && ((workspace) || (n_rows) == 0), FN ": workspace too small (%lld < %lld)", \
-                 (long long)((workspace) ? (workspace_bytes) : 0), (long long)(need))
-#define CW_REQUIRE_ALIGNED8(FN, workspace)                                                                                \
-    WSAE_REQUIRE(((uintptr_t)(workspace) & 7) == 0, FN ": the workspace must be 8-byte aligned")
+// (the workspace's size and alignment: WSAE_REQUIRE_WORKSPACE and WSAE_REQUIRE_WORKSPACE_ALIGNED, wsae_common.h)
 
 }  // namespace

@@ -30,7 +30,15 @@ void wsae_set_error(const char* fmt, ...);
         }                                \
     } while (0)
 
-#define WSAE_LAUNCH_CHECK()                                                                  \
+// FN: the entry point's name, a string literal.  need bytes of workspace; no rows need none, a null workspace counts as 0
+// bytes.  Then its alignment to BYTES, a literal power of two.
+#define WSAE_REQUIRE_WORKSPACE(FN, workspace, workspace_bytes, need, n_rows)                                              \
+    WSAE_REQUIRE((workspace_bytes) >= (need) && ((workspace) || (n_rows) == 0), FN ": workspace too small (%lld < %lld)", \
+                 (long long)((workspace) ? (workspace_bytes) : 0), (long long)(need))
+#define WSAE_REQUIRE_WORKSPACE_ALIGNED(FN, workspace, BYTES) \
+    WSAE_REQUIRE(((uintptr_t)(workspace) & ((BYTES) - 1)) == 0, FN ": the workspace must be " #BYTES "-byte aligned")
+
+#define WSAE_LAUNCH_CHECK()                                                                \
     do {                                                                                     \
         hipError_t e_ = hipGetLastError();                                                   \
         if (e_ != hipSuccess) {                                                              \
@@ -250,6 +258,15 @@ __device__ __forceinline__ float block_sum(float v, float* scratch) {
     if (threadIdx.x == 0)
         for (int i = 0; i < nw; ++i) r += scratch[i];
     return r;
+}
+
+// the maximum of one value per thread of a workgroup of 256, in every thread (a float maximum: any order gives the same
+// bits).  `s_red` holds 4 floats; a second call needs a barrier in between.
+__device__ __forceinline__ float block_max(float v, float* s_red) {
+    v = wave_max(v);
+    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3]));
 }
 
 // load one activation element as float

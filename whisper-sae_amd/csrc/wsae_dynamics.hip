@@ -300,8 +300,8 @@ extern "C" int wsae_dyn_update(const float* vals, const int32_t* idx, int32_t k,
     WSAE_REQUIRE(workspace_bytes >= 0, "wsae_dyn_update: workspace_bytes must not be negative (got %lld)",
                  (long long)workspace_bytes);
     const DynLayout w = dyn_layout(n_rows, k);
-    CW_REQUIRE_WORKSPACE("wsae_dyn_update", workspace, workspace_bytes, w.total, n_rows);
-    CW_REQUIRE_ALIGNED8("wsae_dyn_update", workspace);
+    WSAE_REQUIRE_WORKSPACE("wsae_dyn_update", workspace, workspace_bytes, w.total, n_rows);
+    WSAE_REQUIRE_WORKSPACE_ALIGNED("wsae_dyn_update", workspace, 8);
     if (n_rows == 0) return WSAE_OK;
     char* ws = (char*)workspace;
     DynArgs a = {};
@@ -336,8 +336,8 @@ extern "C" int wsae_boundary_score(const float* nov, const int32_t* seg, const u
     WSAE_REQUIRE(workspace_bytes >= 0, "wsae_boundary_score: workspace_bytes must not be negative (got %lld)",
                  (long long)workspace_bytes);
     const BoundaryLayout w = boundary_layout(n_rows);
-    CW_REQUIRE_WORKSPACE("wsae_boundary_score", workspace, workspace_bytes, w.total, n_rows);
-    CW_REQUIRE_ALIGNED8("wsae_boundary_score", workspace);
+    WSAE_REQUIRE_WORKSPACE("wsae_boundary_score", workspace, workspace_bytes, w.total, n_rows);
+    WSAE_REQUIRE_WORKSPACE_ALIGNED("wsae_boundary_score", workspace, 8);
     if (n_rows == 0) return WSAE_OK;
     char* ws = (char*)workspace;
     unsigned int* count = (unsigned int*)(ws + w.count);

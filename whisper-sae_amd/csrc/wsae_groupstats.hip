@@ -517,7 +517,7 @@ extern "C" int wsae_pool_update(const float* vals, const int32_t* idx, int32_t k
     CW_REQUIRE_WINDOW("wsae_pool_update", f_lo, f_cols, hidden);
     WSAE_REQUIRE(ld >= f_cols, "wsae_pool_update: ld %lld < f_cols %d", (long long)ld, f_cols);
     const int64_t need = 8 * (int64_t)n_seg;
-    CW_REQUIRE_WORKSPACE("wsae_pool_update", workspace, workspace_bytes, need, n_rows);
+    WSAE_REQUIRE_WORKSPACE("wsae_pool_update", workspace, workspace_bytes, need, n_rows);
     if (n_rows == 0) return WSAE_OK;
     hipStream_t st = (hipStream_t)stream;
     int32_t* first = (int32_t*)workspace;

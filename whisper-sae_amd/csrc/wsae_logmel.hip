@@ -25,6 +25,7 @@
 #include <math.h>
 
 #include "wsae_common.h"
+#include "wsae_pcm.h"
 
 // re * re + im * im is two products and one sum, each rounded: the oracle has no fused multiply-add there
 #pragma clang fp contract(off)
@@ -67,12 +68,6 @@ struct LogmelArgs {
     int wt;   // 1: and a wave's 64-byte pieces are whole lines' parts, so the bulk outputs go write-through
 };
 
-template <int DT>
-__device__ __forceinline__ float load_sample(const void* p, int64_t i) {
-    if (DT == WSAE_DT_I16) return (float)__builtin_nontemporal_load((const int16_t*)p + i) * 0x1p-15f;
-    return __builtin_nontemporal_load((const float*)p + i);
-}
-
 __device__ __forceinline__ void store4(float* base, int64_t off, const float4& v, bool wt) {
     if (wt) wt_store4(wt_rsrc(base), off * 4, v);
     else *(float4*)(base + off) = v;
@@ -104,7 +99,7 @@ __global__ __launch_bounds__(LM_BLOCK, 2) void logmel_kernel(LogmelArgs a) {
             int s = q0 + j;
             if (s < 0) s = -s;                          // (at most 200 < P)
             else if (s >= a.P) s = 2 * (a.P - 1) - s;   // negative for the frames of a ragged tile that do not exist
-            s_x[j] = s >= 0 && s < len ? load_sample<DT>(a.x, xu + s) : 0.f;
+            s_x[j] = s >= 0 && s < len ? pcm_load<DT, true>(a.x, xu + s) : 0.f;
         }
     }
 
@@ -194,10 +189,8 @@ __global__ __launch_bounds__(LM_BLOCK, 2) void logmel_kernel(LogmelArgs a) {
             }
         }
     }
-    mx = wave_max(mx);
-    if (lane == 0) s_red[wave] = mx;
-    __syncthreads();
-    if (threadIdx.x == 0) a.tile_max[(int64_t)u * a.tiles + tile] = fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3]));
+    mx = block_max(mx, s_red);
+    if (threadIdx.x == 0) a.tile_max[(int64_t)u * a.tiles + tile] = mx;
 }
 
 template <int NM>
@@ -206,10 +199,7 @@ __global__ __launch_bounds__(LM_BLOCK) void logmel_finish_kernel(LogmelArgs a, i
     const int u = blockIdx.x / chunks, t = (blockIdx.x % chunks) * LM_FIN_FRAMES + 4 * threadIdx.x;
     float mx = -INFINITY;
     for (int i = threadIdx.x; i < a.tiles; i += LM_BLOCK) mx = fmaxf(mx, a.tile_max[(int64_t)u * a.tiles + i]);
-    mx = wave_max(mx);
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = mx;
-    __syncthreads();
-    const float thr = fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3])) - 8.0f;
+    const float thr = block_max(mx, s_red) - 8.0f;
     if (t >= a.T) return;
     float* ou = a.out + (int64_t)u * a.ld_u;
     const bool full = a.vec && t + 3 < a.T;
@@ -252,7 +242,7 @@ extern "C" int wsae_logmel(const void* x, int32_t x_dtype, int32_t n_utt, int64_
                            int64_t n_samples, const float* basis, const float* filt, int32_t n_mels, float* out, int64_t ld_m,
                            int64_t ld_u, float* mel_power, void* workspace, int64_t workspace_bytes, void* stream) {
     WSAE_REQUIRE(x && length && basis && filt && out, "wsae_logmel: null pointer");
-    WSAE_REQUIRE(x_dtype == WSAE_DT_F32 || x_dtype == WSAE_DT_I16, "wsae_logmel: unknown x_dtype %d (float32 or int16)", x_dtype);
+    PCM_REQUIRE_DTYPE("wsae_logmel", x_dtype);
     WSAE_REQUIRE(n_utt >= 0 && n_utt <= LM_MAX_UTT, "wsae_logmel: need 0 <= n_utt <= %d (got %d)", LM_MAX_UTT, n_utt);
     WSAE_REQUIRE(samples_ok(n_samples), "wsae_logmel: n_samples must be a multiple of %d in %d .. %lld (got %lld)", LM_HOP, 3 * LM_HOP,
                  (long long)LM_MAX_SAMPLES, (long long)n_samples);
@@ -264,11 +254,11 @@ extern "C" int wsae_logmel(const void* x, int32_t x_dtype, int32_t n_utt, int64_
     WSAE_REQUIRE(ld_m >= T && ld_m <= LM_MAX_LD_M, "wsae_logmel: need %lld frames <= ld_m <= %lld (got %lld)", (long long)T,
                  (long long)LM_MAX_LD_M, (long long)ld_m);
     WSAE_REQUIRE(ld_u >= n_mels * ld_m, "wsae_logmel: ld_u %lld is below n_mels * ld_m = %lld", (long long)ld_u, (long long)(n_mels * ld_m));
+    PCM_REQUIRE_ELEMENTS_ALIGNED("wsae_logmel", x, x_dtype, out, WSAE_DT_F32);
     WSAE_REQUIRE(((uintptr_t)basis & 15) == 0 && ((uintptr_t)filt & 3) == 0, "wsae_logmel: basis must be 16-byte aligned, filt 4-byte");
     const int64_t need = wsae_logmel_workspace_bytes(n_utt, n_samples, n_mels);
-    WSAE_REQUIRE(workspace_bytes >= need && (workspace || n_utt == 0), "wsae_logmel: workspace too small (%lld < %lld)",
-                 (long long)(workspace ? workspace_bytes : 0), (long long)need);
-    WSAE_REQUIRE(((uintptr_t)workspace & 3) == 0, "wsae_logmel: the workspace must be 4-byte aligned");
+    WSAE_REQUIRE_WORKSPACE("wsae_logmel", workspace, workspace_bytes, need, n_utt);
+    WSAE_REQUIRE_WORKSPACE_ALIGNED("wsae_logmel", workspace, 4);
     if (n_utt == 0) return WSAE_OK;
     const int tiles = (int)ceil_div64(T, LM_TILE), chunks = (int)ceil_div64(T, LM_FIN_FRAMES);
     WSAE_REQUIRE((int64_t)n_utt * tiles <= 0x7fffffffll, "wsae_logmel: n_utt * n_samples is too large for one launch");

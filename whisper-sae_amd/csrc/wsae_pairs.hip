@@ -405,8 +405,8 @@ extern "C" int wsae_pair_top(const uint64_t* keys, const int32_t* cnt, const int
     WSAE_REQUIRE(score >= WSAE_PAIR_COUNT && score <= WSAE_PAIR_MEAN, "wsae_pair_top: unknown score %d", score);
     WSAE_REQUIRE(n >= 1 && n <= WSAE_PAIR_MAX_N, "wsae_pair_top: need 1 <= n <= %d (got %d)", WSAE_PAIR_MAX_N, n);
     const int64_t need = wsae_pair_top_workspace_bytes(cap, n_groups);
-    CW_REQUIRE_WORKSPACE("wsae_pair_top", workspace, workspace_bytes, need, 1);
-    CW_REQUIRE_ALIGNED8("wsae_pair_top", workspace);
+    WSAE_REQUIRE_WORKSPACE("wsae_pair_top", workspace, workspace_bytes, need, 1);
+    WSAE_REQUIRE_WORKSPACE_ALIGNED("wsae_pair_top", workspace, 8);
     hipStream_t st = (hipStream_t)stream;
     const int64_t gb = top_groups_bytes(n_groups);
     unsigned int* count = (unsigned int*)workspace;

@@ -427,8 +427,8 @@ extern "C" int wsae_probe_plan(const float* vals, const int32_t* idx, int32_t k,
     CW_REQUIRE_COLUMN_CODE("wsae_probe_plan", k, hidden, n_rows, col_of, n_cols);
     CW_REQUIRE_LISTS("wsae_probe_plan", cap, t_row, t_val);
     const PlanWs w = plan_ws(n_rows, n_cols);
-    CW_REQUIRE_WORKSPACE("wsae_probe_plan", workspace, workspace_bytes, w.bytes, n_rows);
-    CW_REQUIRE_ALIGNED8("wsae_probe_plan", workspace);
+    WSAE_REQUIRE_WORKSPACE("wsae_probe_plan", workspace, workspace_bytes, w.bytes, n_rows);
+    WSAE_REQUIRE_WORKSPACE_ALIGNED("wsae_probe_plan", workspace, 8);
     if (n_rows == 0) return WSAE_OK;
     hipStream_t st = (hipStream_t)stream;
     int32_t* table = (int32_t*)((char*)workspace + w.off_table);
@@ -499,8 +499,8 @@ extern "C" int wsae_probe_backward(const int64_t* col_ptr, const int32_t* t_row,
     CW_REQUIRE_LISTS("wsae_probe_backward", cap, t_row, t_val);
     WSAE_REQUIRE(lde >= n_classes, "wsae_probe_backward: lde %lld is smaller than the %d classes", (long long)lde, n_classes);
     const BwdWs w = bwd_ws(n_rows, n_cols, n_classes, cap);
-    CW_REQUIRE_WORKSPACE("wsae_probe_backward", workspace, workspace_bytes, w.bytes, n_rows);
-    CW_REQUIRE_ALIGNED8("wsae_probe_backward", workspace);
+    WSAE_REQUIRE_WORKSPACE("wsae_probe_backward", workspace, workspace_bytes, w.bytes, n_rows);
+    WSAE_REQUIRE_WORKSPACE_ALIGNED("wsae_probe_backward", workspace, 8);
     if (n_rows == 0) return WSAE_OK;
     hipStream_t st = (hipStream_t)stream;
     int64_t* job_ptr = (int64_t*)((char*)workspace + w.off_jobs);

@@ -275,7 +275,7 @@ extern "C" int wsae_sample_update(const float* vals, const int32_t* idx, int32_t
                  "wsae_sample_update: the ordinals %lld + [0, %lld) leave [0, 2^31)", (long long)ord_base, (long long)n_rows);
     const int64_t n = n_rows * k, n_lists = (int64_t)f_cols * n_strata;
     const ListHead h = list_head(workspace, n_lists);
-    CW_REQUIRE_WORKSPACE("wsae_sample_update", workspace, workspace_bytes, h.bytes + 12 * n, n_rows);
+    WSAE_REQUIRE_WORKSPACE("wsae_sample_update", workspace, workspace_bytes, h.bytes + 12 * n, n_rows);
     if (n_rows == 0) return WSAE_OK;
     hipStream_t st = (hipStream_t)stream;
     unsigned long long* ent_key = (unsigned long long*)((char*)workspace + h.bytes);

@@ -325,8 +325,8 @@ extern "C" int wsae_gram_update(const float* vals, const int32_t* idx, int32_t k
                  "wsae_gram_update: the row window [%d, %d + %d) is outside [0, %d)", p_lo, p_lo, p_rows, n_cols);
     WSAE_REQUIRE(ldg >= n_cols, "wsae_gram_update: ldg %lld is smaller than the %d columns", (long long)ldg, n_cols);
     const int64_t half = gram_ws_half(n_rows, k);
-    CW_REQUIRE_WORKSPACE("wsae_gram_update", workspace, workspace_bytes, 2 * half, n_rows);
-    CW_REQUIRE_ALIGNED8("wsae_gram_update", workspace);
+    WSAE_REQUIRE_WORKSPACE("wsae_gram_update", workspace, workspace_bytes, 2 * half, n_rows);
+    WSAE_REQUIRE_WORKSPACE_ALIGNED("wsae_gram_update", workspace, 8);
     if (n_rows == 0) return WSAE_OK;
     GramArgs a = {vals, idx, seg, col_of, col_ptr, t_row, t_val, G, (int32_t*)workspace, (float*)((char*)workspace + half),
                   n_rows, cap, ldg, k, hidden, n_cols, p_lo, p_rows};
@@ -368,7 +368,7 @@ extern "C" int wsae_regress_forward(const float* vals, const int32_t* idx, int32
     WSAE_REQUIRE(workspace_bytes >= need && (workspace || need == 0 || n_rows == 0),
                  "wsae_regress_forward: workspace too small (%lld < %lld)", (long long)(workspace ? workspace_bytes : 0),
                  (long long)need);
-    CW_REQUIRE_ALIGNED8("wsae_regress_forward", workspace);
+    WSAE_REQUIRE_WORKSPACE_ALIGNED("wsae_regress_forward", workspace, 8);
     if (n_rows == 0) return WSAE_OK;
     RfArgs a = {vals, idx, seg, Y, col_of, W, bias, pred, (unsigned long long*)n_used, n_rows, ldy, ldw, ldp, k, hidden, lag,
                 n_targets};

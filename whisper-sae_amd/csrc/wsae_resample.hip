@@ -51,26 +51,18 @@ struct ResampleArgs {
     int32_t tile, tiles, span;  // span: floats of LDS behind the staged frames of a tile
 };
 
-template <int DT>
-__device__ __forceinline__ float sample_f32(const void* p, int64_t i) {
-    if constexpr (DT == WSAE_DT_I16) return (float)((const int16_t*)p)[i] * 0x1p-15f;
-    else return ((const float*)p)[i];
-}
-
 // frame m of a row: the channels summed in their order, then one IEEE division
 template <int DT>
 __device__ __forceinline__ float mono_frame(const void* row, int64_t m, int C) {
-    float s = sample_f32<DT>(row, m * C);
+    float s = pcm_load<DT>(row, m * C);
     if (C == 1) return s;
-    for (int c = 1; c < C; ++c) s = s + sample_f32<DT>(row, m * C + c);
+    for (int c = 1; c < C; ++c) s = s + pcm_load<DT>(row, m * C + c);
     return s / (float)C;
 }
 
 // s_x[k] = mono[m_lo + k] for k in [0, span): zeros outside [0, len).  row: element 0 of the utterance.
 template <int DT, int LOAD>
 __device__ __forceinline__ void stage_span(const void* row, int64_t m_lo, int span, int len, int C, float* s_x) {
-    typedef short short8 __attribute__((ext_vector_type(8)));
-    constexpr int ES = DT == WSAE_DT_I16 ? 2 : 4;
     const int tid = threadIdx.x;
     const int ka = (int)min64(max(-m_lo, (int64_t)0), span);          // [ka, kb): the cells with a frame behind them
     const int kb = (int)min64(max((int64_t)len - m_lo, (int64_t)ka), span);
@@ -82,51 +74,10 @@ __device__ __forceinline__ void stage_span(const void* row, int64_t m_lo, int sp
     if constexpr (LOAD == LOAD_ANY) {
         for (int k = tid; k < n; k += RS_BLOCK) s_x[ka + k] = mono_frame<DT>(row, ma + k, C);
     } else {
-        constexpr int CH = LOAD == LOAD_VEC2 ? 2 : 1, FB = CH * ES, FV = 16 / FB;  // bytes per frame, frames per vector
-        const char* p = (const char*)row + ma * FB;
-        const int lead = min((int)(((16 - ((uintptr_t)p & 15)) & 15) / FB), n);  // (the host chose this route: FB divides it)
-        const int nvec = (n - lead) / FV, done = lead + nvec * FV;
-        if (tid < lead) s_x[ka + tid] = mono_frame<DT>(row, ma + tid, CH);
-        if (done + tid < n) s_x[ka + done + tid] = mono_frame<DT>(row, ma + done + tid, CH);
-        const char* pv = p + lead * FB;
-        float* sv = s_x + ka + lead;
-        for (int v0 = tid; v0 < nvec; v0 += 4 * RS_BLOCK) {
-            if constexpr (DT == WSAE_DT_I16) {
-                short8 q[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (v0 + k * RS_BLOCK < nvec) q[k] = ((const short8*)pv)[v0 + k * RS_BLOCK];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const int v = v0 + k * RS_BLOCK;
-                    if (v < nvec) {
-#pragma unroll
-                        for (int i = 0; i < FV; ++i) {
-                            float s = (float)q[k][CH * i] * 0x1p-15f;
-                            if constexpr (CH == 2) s = (s + (float)q[k][2 * i + 1] * 0x1p-15f) / 2.0f;
-                            sv[v * FV + i] = s;
-                        }
-                    }
-                }
-            } else {
-                f32x4 q[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (v0 + k * RS_BLOCK < nvec) q[k] = ((const f32x4*)pv)[v0 + k * RS_BLOCK];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const int v = v0 + k * RS_BLOCK;
-                    if (v < nvec) {
-#pragma unroll
-                        for (int i = 0; i < FV; ++i) {
-                            float s = q[k][CH * i];
-                            if constexpr (CH == 2) s = (s + q[k][2 * i + 1]) / 2.0f;
-                            sv[v * FV + i] = s;
-                        }
-                    }
-                }
-            }
-        }
+        // (the host chose this route: the row's frames meet the 16-byte boundaries)
+        constexpr int CH = LOAD == LOAD_VEC2 ? 2 : 1;
+        float* sv = s_x + ka;
+        pcm_for_span<DT, CH, RS_BLOCK, 4>((const typename PcmIn<DT>::elem*)row + ma * CH, n, [&](int k, float s) { sv[k] = s; });
     }
 }
 
@@ -193,8 +144,6 @@ __global__ __launch_bounds__(RS_BLOCK) void resample_kernel(ResampleArgs a) {
     st.store(s_y);
 }
 
-inline bool dtype_ok(int dt) { return dt == WSAE_DT_F32 || dt == WSAE_DT_I16; }
-
 // the most blocks a run of `tile` outputs touches, whatever its first output
 inline int64_t blocks_of(int64_t tile, int64_t new_) { return tile % new_ == 0 ? tile / new_ : (tile + 2 * new_ - 2) / new_; }
 
@@ -230,9 +179,9 @@ extern "C" int wsae_resample(const void* x, int32_t x_dtype, int32_t n_utt, int6
                              int32_t n_taps, int32_t halo, void* out, int32_t out_dtype, int64_t ld_y, int64_t out_cols,
                              int32_t* out_len, void* stream) {
     WSAE_REQUIRE(x && length && taps && first && out && out_len, "wsae_resample: null pointer");
-    WSAE_REQUIRE(dtype_ok(x_dtype), "wsae_resample: unknown x_dtype %d (float32 or int16)", x_dtype);
-    WSAE_REQUIRE(dtype_ok(out_dtype), "wsae_resample: unknown out_dtype %d (float32 or int16)", out_dtype);
-    WSAE_REQUIRE(n_utt >= 0, "wsae_resample: n_utt must not be negative (got %d)", n_utt);
+    PCM_REQUIRE_DTYPE("wsae_resample", x_dtype);
+    PCM_REQUIRE_DTYPE("wsae_resample", out_dtype);
+    PCM_REQUIRE_N_UTT("wsae_resample", n_utt);
     WSAE_REQUIRE(channels >= 1 && channels <= WSAE_RESAMPLE_MAX_CHANNELS, "wsae_resample: need 1 <= channels <= %d (got %d)",
                  WSAE_RESAMPLE_MAX_CHANNELS, channels);
     WSAE_REQUIRE(orig >= 1 && orig <= WSAE_RESAMPLE_MAX_RATE, "wsae_resample: need 1 <= orig <= %d (got %d)", WSAE_RESAMPLE_MAX_RATE, orig);
@@ -244,19 +193,15 @@ extern "C" int wsae_resample(const void* x, int32_t x_dtype, int32_t n_utt, int6
     WSAE_REQUIRE(halo >= 0 && halo <= WSAE_RESAMPLE_MAX_HALO, "wsae_resample: need 0 <= halo <= %d (got %d)", WSAE_RESAMPLE_MAX_HALO, halo);
     WSAE_REQUIRE(n_taps <= orig + 2 * halo, "wsae_resample: n_taps %d does not fit the staged span of a block, orig + 2 halo = %d",
                  n_taps, orig + 2 * halo);
-    WSAE_REQUIRE(max_length >= 0 && max_length <= 0x7fffffffll, "wsae_resample: need 0 <= max_length < 2^31 (got %lld)",
-                 (long long)max_length);
-    WSAE_REQUIRE(ld_x >= max_length * channels, "wsae_resample: ld_x %lld is below max_length * channels = %lld", (long long)ld_x,
-                 (long long)(max_length * channels));
+    PCM_REQUIRE_MAX_LENGTH("wsae_resample", max_length);
+    PCM_REQUIRE_LD_X("wsae_resample", ld_x, max_length * channels, "max_length * channels =");
     const int64_t need_cols = ceil_div64((int64_t)new_ * max_length, orig);
     WSAE_REQUIRE(out_cols >= need_cols && out_cols <= 0x7fffffffll,
                  "wsae_resample: need ceil(new_ * max_length / orig) = %lld <= out_cols < 2^31 (got %lld)", (long long)need_cols,
                  (long long)out_cols);
     WSAE_REQUIRE(out_cols <= ld_y, "wsae_resample: out_cols %lld is above ld_y %lld", (long long)out_cols, (long long)ld_y);
-    const uintptr_t xa = x_dtype == WSAE_DT_I16 ? 1 : 3, oa = out_dtype == WSAE_DT_I16 ? 1 : 3;
-    WSAE_REQUIRE(((uintptr_t)x & xa) == 0 && ((uintptr_t)out & oa) == 0, "wsae_resample: x and out must be aligned to their elements");
-    WSAE_REQUIRE((((uintptr_t)length | (uintptr_t)taps | (uintptr_t)first | (uintptr_t)out_len) & 3) == 0,
-                 "wsae_resample: length, taps, first and out_len must be 4-byte aligned");
+    PCM_REQUIRE_ELEMENTS_ALIGNED("wsae_resample", x, x_dtype, out, out_dtype);
+    PCM_REQUIRE_TABLES_ALIGNED("wsae_resample", ptr_bits(length, taps, first, out_len), 0, "length, taps, first and out_len must be 4-byte aligned");
 
     // the route: the largest tile whose span fits beside the output stage, and the table beside that where it fits too
     int64_t tile = RS_TILE, span;

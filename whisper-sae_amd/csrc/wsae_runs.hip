@@ -287,7 +287,7 @@ extern "C" int wsae_runs_update(const float* vals, const int32_t* idx, int32_t k
                  "wsae_runs_update: ev_cap %lld needs the event buffers and the cursor (null pointer)", (long long)ev_cap);
     WSAE_REQUIRE(ev_min_len >= 1, "wsae_runs_update: ev_min_len must be at least 1 (got %d)", ev_min_len);
     const int64_t need = 8 * (int64_t)n_seg;
-    CW_REQUIRE_WORKSPACE("wsae_runs_update", workspace, workspace_bytes, need, n_rows);
+    WSAE_REQUIRE_WORKSPACE("wsae_runs_update", workspace, workspace_bytes, need, n_rows);
     if (n_rows == 0) return WSAE_OK;
     hipStream_t st = (hipStream_t)stream;
     int32_t* first = (int32_t*)workspace;

@@ -326,8 +326,8 @@ extern "C" int wsae_sta_update(const float* vals, const int32_t* idx, int32_t k,
     WSAE_REQUIRE(weight == WSAE_STA_WEIGHT_VALUE || weight == WSAE_STA_WEIGHT_ONE,
                  "wsae_sta_update: weight must be WSAE_STA_WEIGHT_VALUE or WSAE_STA_WEIGHT_ONE (got %d)", weight);
     const StaPlan p = sta_plan(n_rows, k, f_cols);
-    CW_REQUIRE_WORKSPACE("wsae_sta_update", workspace, workspace_bytes, p.bytes, n_rows);
-    CW_REQUIRE_ALIGNED8("wsae_sta_update", workspace);
+    WSAE_REQUIRE_WORKSPACE("wsae_sta_update", workspace, workspace_bytes, p.bytes, n_rows);
+    WSAE_REQUIRE_WORKSPACE_ALIGNED("wsae_sta_update", workspace, 8);
     if (n_rows == 0) return WSAE_OK;
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;

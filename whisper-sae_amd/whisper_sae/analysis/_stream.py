@@ -13,20 +13,10 @@ import torch
 from torch import Tensor
 
 from .. import _native as N
+from .._device import grow, need_gpu, workspace  # noqa: F401  (the trackers take them from here)
 from ..sae.engine import require_device_tensor
 
 MAX_ROWS = 2 ** 31 - 1  # the int32 range: the rows of one call, and the frames an int32 state counts in all
-
-
-def need_gpu(what: str, dev: Optional[torch.device]) -> torch.device:
-    if dev is None:
-        if not torch.cuda.is_available():
-            raise N.WsaeError(f"{what} needs a GPU: its kernels run on the device and there is no CPU implementation")
-        dev = torch.device("cuda", torch.cuda.current_device())
-    if dev.type != "cuda":
-        raise N.WsaeError(f"{what} cannot run on '{dev}': its kernels run on the GPU only")
-    N.lib()  # fail loudly when the HIP library is not built
-    return dev
 
 
 def feature_window(window, hidden: int, name: str = "f_window") -> Tuple[int, int]:
@@ -150,19 +140,6 @@ def take_form(tracker, vals: Tensor, why: str = "") -> str:
         raise ValueError(f"this tracker has taken {tracker._form} updates: [n_utt, T, k] codes and flat codes with segments "
                          f"{why}cannot be mixed")
     return form
-
-
-def grow(tracker, elems: int, dtype, dev) -> Tensor:
-    """``tracker._ws`` with at least ``elems`` elements of ``dtype``."""
-    if tracker._ws is None or tracker._ws.numel() < elems:
-        tracker._ws = None  # (release before the larger one is taken)
-        tracker._ws = torch.empty(elems, dtype=dtype, device=dev)
-    return tracker._ws
-
-
-def workspace(tracker, nbytes: int, dev) -> Tensor:
-    """``tracker._ws`` as at least ``nbytes`` bytes (one at least, so that it has an address)."""
-    return grow(tracker, max(int(nbytes), 1), torch.uint8, dev)
 
 
 def transposed_plan(tracker, v: Tensor, i: Tensor, k: int, seg: Tensor, rows: int):

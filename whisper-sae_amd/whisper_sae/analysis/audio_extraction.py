@@ -30,11 +30,11 @@ import torch
 from torch import Tensor
 
 from .. import _native as N
-from ..data.audio import HOP, _need_gpu
+from .._device import workspace
+from ..data.audio import HOP
+from ..data.waveforms import _DTYPES, pack_waveforms
 from .feature_viz import FeatureActivation, TopKTracker
 from .temporal import FeatureEvents
-
-_DTYPES = {torch.float32: N.DT_F32, torch.int16: N.DT_I16}
 
 
 @dataclass
@@ -75,48 +75,14 @@ class WaveformBank:
     the valid samples of each row (default ``S``; from the list itself when a list is given)."""
 
     def __init__(self, waveforms: Union[Tensor, Sequence[Tensor]], lengths=None, device="cuda"):
-        sizes = None
-        if isinstance(waveforms, (list, tuple)):
-            if lengths is not None:
-                raise ValueError("lengths come from the waveforms themselves when a list is given")
-            if not waveforms:
-                raise ValueError("the list of waveforms is empty")
-            for i, w in enumerate(waveforms):
-                if not isinstance(w, Tensor) or w.dim() != 1:
-                    raise ValueError(f"waveform {i} must be a 1-D tensor, got "
-                                     f"{tuple(w.shape) if isinstance(w, Tensor) else type(w).__name__}")
-                if w.dtype != waveforms[0].dtype:
-                    raise ValueError(f"waveform {i} is {w.dtype}, waveform 0 is {waveforms[0].dtype}")
-            if waveforms[0].dtype not in _DTYPES:
-                raise ValueError(f"waveforms must be float32 or int16, got {waveforms[0].dtype}")
-            sizes = [int(w.numel()) for w in waveforms]
-        else:
-            if not isinstance(waveforms, Tensor) or waveforms.dim() != 2:
-                raise ValueError(f"waveforms must be [n_utt, samples] or a list of 1-D tensors, got "
-                                 f"{tuple(waveforms.shape) if isinstance(waveforms, Tensor) else type(waveforms).__name__}")
-            if waveforms.dtype not in _DTYPES:
-                raise ValueError(f"waveforms must be float32 or int16, got {waveforms.dtype}")
-            if lengths is not None and torch.as_tensor(lengths).numel() != waveforms.shape[0]:
-                raise ValueError(f"lengths has {torch.as_tensor(lengths).numel()} entries for {waveforms.shape[0]} utterances")
-        self.device = _need_gpu("WaveformBank", torch.device(device))
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        if sizes is not None:
-            packed = torch.zeros(len(waveforms), max(max(sizes), 1), dtype=waveforms[0].dtype, device=self.device)
-            for i, w in enumerate(waveforms):
-                packed[i, :sizes[i]] = w.to(self.device)
-            waveforms, lengths = packed, torch.tensor(sizes, dtype=torch.int32)
-        n_utt, s = waveforms.shape
-        if s == 0:  # (nothing to point the kernel at: one column of zeros, no valid sample)
-            waveforms, lengths, s = waveforms.new_zeros(n_utt, 1), torch.zeros(n_utt, dtype=torch.int32), 1
-        if lengths is None:
-            lengths = torch.full((n_utt,), s, dtype=torch.int32)
-        else:
-            lengths = torch.as_tensor(lengths).reshape(-1)
-        self.samples = waveforms.to(self.device).contiguous()
-        self.lengths = lengths.to(device=self.device, dtype=torch.int32).contiguous()
-        self.n_utt, self.max_length = int(n_utt), int(s)
-        self._workspace: Optional[Tensor] = None
+        self.samples, self.lengths, self.n_utt, self.max_length, _ = pack_waveforms("WaveformBank", waveforms, lengths, device,
+                                                                                   host=True, contiguous=True)
+        self.device = self.samples.device
+        self._ws: Optional[Tensor] = None
+
+    @property
+    def _workspace(self) -> Optional[Tensor]:  # (the name the buffer had before it became the shared ``_ws``)
+        return self._ws
 
     @property
     def dtype(self) -> torch.dtype:
@@ -184,8 +150,7 @@ def cut_clips(bank: WaveformBank, utt, start, count, *, normalize: bool = True, 
     need = lib.wsae_clip_workspace_bytes(n_clips, max_count)
     if need < 0:
         raise N.WsaeError(f"wsae_clip_workspace_bytes rejects n_clips={n_clips} max_count={max_count}")
-    if bank._workspace is None or bank._workspace.numel() * 4 < need:
-        bank._workspace = torch.empty((need + 3) // 4, dtype=torch.float32, device=dev)
+    ws = workspace(bank, need, dev)
     x = bank.samples
     out = samples if samples.numel() else torch.zeros(1, dtype=out_dtype, device=dev)  # (a non-null address)
     with torch.cuda.device(dev):
@@ -194,7 +159,7 @@ def cut_clips(bank: WaveformBank, utt, start, count, *, normalize: bool = True, 
                                       count.data_ptr(), max_count, offsets.data_ptr(),
                                       N.CLIP_GAIN_PEAK if normalize else N.CLIP_GAIN_NONE, target, fade, out.data_ptr(),
                                       _DTYPES[out_dtype], samples.numel(), lengths.data_ptr(), peaks.data_ptr(),
-                                      bank._workspace.data_ptr(), bank._workspace.numel() * 4,
+                                      ws.data_ptr(), ws.numel(),
                                       torch.cuda.current_stream(dev).cuda_stream), "wsae_clip_extract")
     return ClipBatch(samples, offsets, lengths, peaks)
 

@@ -20,12 +20,12 @@ import torch
 from torch import Tensor
 
 from .. import _native as N
+from .._device import gpu_device, workspace
+from .waveforms import _DTYPES, head_device, pack_waveforms
 
 N_FFT, HOP, N_BINS, SAMPLE_RATE = N.LOGMEL_NFFT, N.LOGMEL_HOP, N.LOGMEL_BINS, 16000
 N_SAMPLES = 30 * SAMPLE_RATE  # Whisper's 30 s window
 MEL_PER_ENCODER_FRAME = 2     # the encoder's second convolution has stride 2
-
-_DTYPES = {torch.float32: N.DT_F32, torch.int16: N.DT_I16}
 
 
 def _slaney_mel(hz):
@@ -100,13 +100,6 @@ def sample_span_of_frames(first: int, last: int, stride: int = MEL_PER_ENCODER_F
     return int(first) * step, (int(last) + 1) * step
 
 
-def _need_gpu(what: str, dev: torch.device) -> torch.device:
-    if dev.type != "cuda":
-        raise N.WsaeError(f"{what} cannot run on '{dev}': its kernels run on the GPU only")
-    N.lib()  # fail loudly when the HIP library is not built
-    return dev
-
-
 class LogMel:
     """``LogMel(n_mels)(waveforms, lengths) -> [n_utt, n_mels, n_samples / 160]`` float32 on ``device``.
 
@@ -126,54 +119,16 @@ class LogMel:
         table = torch.as_tensor(dft_basis() if basis is None else basis)
         if tuple(table.shape) != (N_FFT, N.LOGMEL_COLS):
             raise ValueError(f"basis must be [{N_FFT}, {N.LOGMEL_COLS}], got {tuple(table.shape)}")
-        self.device = _need_gpu("LogMel", torch.device(device))
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = gpu_device("LogMel", device)
         self.n_mels, self.n_samples, self.frames = n_mels, n_samples, n_samples // HOP
         self.filters = filt.to(device=self.device, dtype=torch.float32).contiguous()
         self.basis = table.to(device=self.device, dtype=torch.float32).contiguous()
-        self._workspace: Optional[Tensor] = None
+        self._ws: Optional[Tensor] = None
 
-    def _pack(self, waveforms, lengths) -> Tuple[Tensor, Tensor]:
-        if isinstance(waveforms, (list, tuple)):
-            if lengths is not None:
-                raise ValueError("lengths come from the waveforms themselves when a list is given")
-            if not waveforms:
-                raise ValueError("the list of waveforms is empty")
-            for i, w in enumerate(waveforms):
-                if not isinstance(w, Tensor) or w.dim() != 1:
-                    raise ValueError(f"waveform {i} must be a 1-D tensor, got {tuple(w.shape) if isinstance(w, Tensor) else type(w).__name__}")
-                if w.dtype != waveforms[0].dtype:
-                    raise ValueError(f"waveform {i} is {w.dtype}, waveform 0 is {waveforms[0].dtype}")
-                _need_gpu("LogMel", w.device)
-            sizes = [int(w.numel()) for w in waveforms]
-            packed = torch.zeros(len(waveforms), max(max(sizes), 1), dtype=waveforms[0].dtype, device=self.device)
-            for i, w in enumerate(waveforms):
-                packed[i, :sizes[i]] = w
-            waveforms, lengths = packed, torch.tensor(sizes, dtype=torch.int32)
-        if not isinstance(waveforms, Tensor) or waveforms.dim() != 2:
-            raise ValueError(f"waveforms must be [n_utt, samples] or a list of 1-D tensors, got "
-                             f"{tuple(waveforms.shape) if isinstance(waveforms, Tensor) else type(waveforms).__name__}")
-        _need_gpu("LogMel", waveforms.device)
-        if waveforms.device != self.device:
-            raise ValueError(f"waveforms are on {waveforms.device}, this LogMel on {self.device}")
-        if waveforms.dtype not in _DTYPES:
-            raise ValueError(f"waveforms must be float32 or int16, got {waveforms.dtype}")
-        n_utt, s = waveforms.shape
-        if s == 0:  # (nothing to point the kernel at: one column of zeros, no valid sample)
-            waveforms, lengths, s = waveforms.new_zeros(n_utt, 1), torch.zeros(n_utt, dtype=torch.int32), 1
-        if s > self.n_samples:
-            raise ValueError(f"waveforms have {s} samples, this LogMel takes at most n_samples = {self.n_samples}")
-        if lengths is None:
-            lengths = torch.full((n_utt,), s, dtype=torch.int32, device=self.device)
-        else:
-            lengths = torch.as_tensor(lengths).reshape(-1)
-            if lengths.numel() != n_utt:
-                raise ValueError(f"lengths has {lengths.numel()} entries for {n_utt} utterances")
-            lengths = lengths.to(device=self.device, dtype=torch.int32).contiguous()
-        if waveforms.stride(1) != 1 and s > 1 or (n_utt > 1 and waveforms.stride(0) < s):
-            waveforms = waveforms.contiguous()
-        return waveforms, lengths
+    @staticmethod
+    def is_waveform(t) -> bool:
+        """Whether ``t`` is a batch of waveforms ``[n_utt, S]`` (and not of mel features, which are 3-D)."""
+        return isinstance(t, Tensor) and t.dim() == 2
 
     def __call__(self, waveforms: Union[Tensor, Sequence[Tensor]], lengths=None, *, out: Optional[Tensor] = None,
                  return_power: bool = False):
@@ -182,8 +137,7 @@ class LogMel:
         (default ``S``; values above ``S`` are clamped to it).  ``out``: a float32 ``[n_utt, n_mels, frames]`` tensor (or
         view with unit stride along the frames) to write into.  With ``return_power`` the result is ``(features,
         mel_power)``, the second the mel energies before floor and log."""
-        x, lengths = self._pack(waveforms, lengths)
-        n_utt, s = x.shape
+        x, lengths, n_utt, s, _ = pack_waveforms("LogMel", waveforms, lengths, self.device, max_samples=self.n_samples)
         shape = (n_utt, self.n_mels, self.frames)
         if out is None:
             out = torch.empty(shape, dtype=torch.float32, device=self.device)
@@ -206,14 +160,13 @@ class LogMel:
         need = lib.wsae_logmel_workspace_bytes(n_utt, self.n_samples, self.n_mels)
         if need < 0:
             raise N.WsaeError(f"wsae_logmel_workspace_bytes rejects n_utt={n_utt} n_samples={self.n_samples} n_mels={self.n_mels}")
-        if self._workspace is None or self._workspace.numel() * 4 < need:
-            self._workspace = torch.empty((need + 3) // 4, dtype=torch.float32, device=self.device)
+        ws = workspace(self, need, self.device)
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
             N.check(lib.wsae_logmel(x.data_ptr(), _DTYPES[x.dtype], n_utt, x.stride(0) if n_utt > 1 else max(x.stride(0), s, 1),
                                     lengths.data_ptr(), s, self.n_samples, self.basis.data_ptr(), self.filters.data_ptr(),
-                                    self.n_mels, out.data_ptr(), ld_m, ld_u, N.ptr(power), self._workspace.data_ptr(),
-                                    self._workspace.numel() * 4, stream), "wsae_logmel")
+                                    self.n_mels, out.data_ptr(), ld_m, ld_u, N.ptr(power), ws.data_ptr(), ws.numel(),
+                                    stream), "wsae_logmel")
         if return_power:
             return out, power.as_strided(shape, (ld_u, ld_m, 1))
         return out
@@ -223,10 +176,7 @@ def log_mel_spectrogram(waveforms, lengths=None, *, n_mels: int = 80, device=Non
                         **kw):
     """One-shot ``LogMel(n_mels, device, n_samples, filters)(waveforms, lengths, **kw)``; ``device`` defaults to that of
     the waveforms.  Build a ``LogMel`` once where more than one batch is converted: it keeps the tables on the device."""
-    if device is None:
-        first = waveforms[0] if isinstance(waveforms, (list, tuple)) and waveforms else waveforms
-        device = first.device if isinstance(first, Tensor) else "cuda"
-    return LogMel(n_mels, device, n_samples, filters)(waveforms, lengths, **kw)
+    return LogMel(n_mels, head_device(waveforms) if device is None else device, n_samples, filters)(waveforms, lengths, **kw)
 
 
 def features_from_batch(frontend: Optional[LogMel], batch):
@@ -236,13 +186,8 @@ def features_from_batch(frontend: Optional[LogMel], batch):
     ``AudioFrontEnd`` also converts the 3-D tensors that are interleaved waveforms ``[n_utt, S, C]`` (its ``is_waveform``)."""
     if frontend is None:
         return batch[0] if isinstance(batch, (list, tuple)) else batch
-    from .resample import AudioFrontEnd
     first = batch[0] if isinstance(batch, (list, tuple)) else batch
-    if isinstance(frontend, AudioFrontEnd):
-        wave = frontend.is_waveform(first)
-    else:
-        wave = isinstance(first, Tensor) and first.dim() == 2
-    if not wave:
+    if not frontend.is_waveform(first):
         return first
     return frontend(first, batch[1] if isinstance(batch, (list, tuple)) and len(batch) > 1 else None)
 

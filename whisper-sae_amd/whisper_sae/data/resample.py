@@ -17,7 +17,9 @@ import torch
 from torch import Tensor
 
 from .. import _native as N
-from .audio import N_SAMPLES, SAMPLE_RATE, LogMel, _DTYPES, _need_gpu
+from .._device import gpu_device
+from .audio import N_SAMPLES, SAMPLE_RATE, LogMel
+from .waveforms import _DTYPES, head, head_device, pack_waveforms
 
 
 def _reduced(orig_freq, new_freq) -> Tuple[int, int]:
@@ -95,61 +97,13 @@ class Resampler:
         if taps.shape[1] > N.RESAMPLE_MAX_TAPS or halo > N.RESAMPLE_MAX_HALO:
             raise ValueError(f"{orig_freq} -> {new_freq} needs {taps.shape[1]} taps per phase and a halo of {halo}: at most "
                              f"{N.RESAMPLE_MAX_TAPS} and {N.RESAMPLE_MAX_HALO} are served")
-        self.device = _need_gpu("Resampler", torch.device(device))
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = gpu_device("Resampler", device)
         self.n_taps, self.halo = int(taps.shape[1]), int(halo)
         self.taps = torch.from_numpy(taps).to(self.device).contiguous()
         self.first = torch.from_numpy(first).to(self.device).contiguous()
 
     def out_cols(self, samples: int) -> int:
         return -((-self.new * int(samples)) // self.orig)
-
-    def _pack(self, waveforms, lengths) -> Tuple[Tensor, Tensor, int, int]:
-        """``(x [n_utt, S, C] with interleaved frames, lengths, S, C)``."""
-        if isinstance(waveforms, (list, tuple)):
-            if lengths is not None:
-                raise ValueError("lengths come from the waveforms themselves when a list is given")
-            if not waveforms:
-                raise ValueError("the list of waveforms is empty")
-            for i, w in enumerate(waveforms):
-                if not isinstance(w, Tensor) or w.dim() not in (1, 2):
-                    raise ValueError(f"waveform {i} must be a 1-D or [samples, channels] tensor, got "
-                                     f"{tuple(w.shape) if isinstance(w, Tensor) else type(w).__name__}")
-                if w.dtype != waveforms[0].dtype:
-                    raise ValueError(f"waveform {i} is {w.dtype}, waveform 0 is {waveforms[0].dtype}")
-                if w.shape[1:] != waveforms[0].shape[1:]:
-                    raise ValueError(f"waveform {i} is {tuple(w.shape)}, waveform 0 is {tuple(waveforms[0].shape)}: the channels differ")
-                _need_gpu("Resampler", w.device)
-            sizes = [int(w.shape[0]) for w in waveforms]
-            packed = torch.zeros((len(waveforms), max(sizes)) + tuple(waveforms[0].shape[1:]), dtype=waveforms[0].dtype,
-                                 device=self.device)
-            for i, w in enumerate(waveforms):
-                packed[i, :sizes[i]] = w
-            waveforms, lengths = packed, torch.tensor(sizes, dtype=torch.int32)
-        if not isinstance(waveforms, Tensor) or waveforms.dim() not in (2, 3):
-            raise ValueError(f"waveforms must be [n_utt, samples], [n_utt, samples, channels] or a list of such rows, got "
-                             f"{tuple(waveforms.shape) if isinstance(waveforms, Tensor) else type(waveforms).__name__}")
-        _need_gpu("Resampler", waveforms.device)
-        if waveforms.device != self.device:
-            raise ValueError(f"waveforms are on {waveforms.device}, this Resampler on {self.device}")
-        if waveforms.dtype not in _DTYPES:
-            raise ValueError(f"waveforms must be float32 or int16, got {waveforms.dtype}")
-        n_utt, s = waveforms.shape[:2]
-        c = waveforms.shape[2] if waveforms.dim() == 3 else 1
-        if not 1 <= c <= N.RESAMPLE_MAX_CHANNELS:
-            raise ValueError(f"waveforms have {c} channels, 1 to {N.RESAMPLE_MAX_CHANNELS} are served")
-        if lengths is None:
-            lengths = torch.full((n_utt,), s, dtype=torch.int32, device=self.device)
-        else:
-            lengths = torch.as_tensor(lengths).reshape(-1)
-            if lengths.numel() != n_utt:
-                raise ValueError(f"lengths has {lengths.numel()} entries for {n_utt} utterances")
-            lengths = lengths.to(device=self.device, dtype=torch.int32).contiguous()
-        x = waveforms.unsqueeze(2) if waveforms.dim() == 2 else waveforms
-        if not ((c == 1 or x.stride(2) == 1) and (s <= 1 or x.stride(1) == c) and (n_utt <= 1 or x.stride(0) >= s * c)):
-            x = x.contiguous()  # (frames interleaved, rows that do not overlap)
-        return x, lengths, s, c
 
     def __call__(self, waveforms: Union[Tensor, Sequence[Tensor]], lengths=None, *, out: Optional[Tensor] = None,
                  out_dtype: Optional[torch.dtype] = None) -> Tuple[Tensor, Tensor]:
@@ -158,8 +112,7 @@ class Resampler:
         values above ``S`` are clamped to it).  ``out``: a float32 or int16 ``[n_utt, ceil(new S / orig)]`` tensor (or view
         with unit stride along the samples) to write into; ``out_dtype`` (default float32) where there is none.  The result
         is ``(y, out_lengths)``: ``y`` is zero from ``out_lengths[u]`` on; int16 is ``rint(y * 32768)``, saturated."""
-        x, lengths, s, c = self._pack(waveforms, lengths)
-        n_utt = x.shape[0]
+        x, lengths, n_utt, s, c = pack_waveforms("Resampler", waveforms, lengths, self.device, channels=True, keep_empty=True)
         shape = (n_utt, self.out_cols(s))
         if out is None:
             out_dtype = torch.float32 if out_dtype is None else out_dtype
@@ -193,10 +146,7 @@ def resample(waveforms, orig_freq: int, new_freq: int = SAMPLE_RATE, lengths=Non
              rolloff: float = 0.99, **kw):
     """One-shot ``Resampler(orig_freq, new_freq, device, ...)(waveforms, lengths, **kw)``; ``device`` defaults to that of the
     waveforms.  Build a ``Resampler`` once where more than one batch is converted: it keeps the tables on the device."""
-    if device is None:
-        head = waveforms[0] if isinstance(waveforms, (list, tuple)) and waveforms else waveforms
-        device = head.device if isinstance(head, Tensor) else "cuda"
-    return Resampler(orig_freq, new_freq, device, lowpass_filter_width, rolloff)(waveforms, lengths, **kw)
+    return Resampler(orig_freq, new_freq, head_device(waveforms) if device is None else device, lowpass_filter_width, rolloff)(waveforms, lengths, **kw)
 
 
 class AudioFrontEnd:
@@ -217,8 +167,8 @@ class AudioFrontEnd:
         return isinstance(t, Tensor) and (t.dim() == 2 or (t.dim() == 3 and t.shape[2] <= N.RESAMPLE_MAX_CHANNELS))
 
     def __call__(self, waveforms, lengths=None, *, out: Optional[Tensor] = None, return_power: bool = False):
-        head = waveforms[0] if isinstance(waveforms, (list, tuple)) and waveforms else waveforms
-        mono = isinstance(head, Tensor) and head.dim() == (1 if isinstance(waveforms, (list, tuple)) else 2)
+        first = head(waveforms)
+        mono = isinstance(first, Tensor) and first.dim() == (1 if isinstance(waveforms, (list, tuple)) else 2)
         if not (mono and self.resampler.orig == self.resampler.new):
             waveforms, lengths = self.resampler(waveforms, lengths)
         return self.logmel(waveforms, lengths, out=out, return_power=return_power)
